@@ -21,11 +21,17 @@ weak scaling.  No collective in the apply loop; RCCL (libmtgpu mt_comm, over xGM
 per-document checksums to rank 0 at the end and provides the barrier and max-over-ranks clock.
 No process imports torch: libmtgpu's HIP runtime is the only one.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant apply kernel against HBM with the
-algorithmic bytes it must move per launch (DESIGN.md "Roofline accounting"); `cpu_baseline`
-replays a bounded sample of the same logs on the CPU oracle (oracle/mtcpu.cpp, a port of the
-reference's observer path) with every host core, and the GPU's checksums for that sample are
-checked against it (`parity`).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the `--steps` steps and prints
+the headline figure (`value`, `ms_per_step`) with the checksum digest of the documents; with
+`--dump-outputs DIR` it also writes what the last timed step computed (see dump_outputs).
+
+`--full` adds everything else the line can carry, each from runs of its own after the timed steps:
+`value_hbm_resident` (the same steps with the log resident in HBM, checked equal to the host-fed
+ones); `roofline`, which prices the dominant apply kernel against HBM with the algorithmic bytes it
+must move per launch (DESIGN.md "Roofline accounting"); `cpu_baseline`, which replays a bounded
+sample of the same logs on the CPU oracle (oracle/mtcpu.cpp, a port of the reference's observer
+path) with every host core, the GPU's checksums for that sample checked against it (`parity`); and
+on the default C3 shape the `slow_paths` side lines.
 """
 import argparse
 import json
@@ -135,8 +141,13 @@ def parse():
     p.add_argument('--docs', type=int, default=0, help='documents per GPU (default: the config)')
     p.add_argument('--ops', type=int, default=0, help='ops per document (default: the config)')
     p.add_argument('--ops-per-launch', type=int, default=32)
-    p.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the cpu_baseline sample')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also measure and check everything beside the headline figure: the '
+                        'HBM-resident steps, the roofline step, the CPU baseline and parity, the side lines')
+    p.add_argument('--dump-outputs', metavar='DIR', default='',
+                   help='write what the last timed step computed as DIR/<name>.npy (float64)')
+    p.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: budget of the cpu_baseline sample')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the cpu_baseline leg')
     p.add_argument('--seed', type=int, default=20261015)
     p.add_argument('--comm', choices=['auto', 'rccl', 'gloo'], default='auto',
                    help='rank exchange: RCCL over xGMI (default for N > 1; "rccl" also at N = 1, a one-rank '
@@ -150,7 +161,7 @@ def parse():
                         'min(b, N << t) ops per document; 0: none -- the ramp measured slower on C3 and C5, '
                         'profiles/r06_ab/ab9_*)')
     p.add_argument('--no-slow-paths', action='store_true',
-                   help='skip the N=1 side lines for the paths off the narrow register engine (C3 with delta '
+                   help='--full without the N=1 side lines for the paths off the narrow register engine (C3 with delta '
                         'events recorded, C3 with 48 clients, the editing-client farm at 100K documents)')
     return p.parse_args()
 
@@ -306,46 +317,56 @@ def main():
     elapsed, kern_ms, wall_ms, launches, alg_bytes, cls = timed(main_step)
     cs_fed = eng.checksums()
     tk_ok = bool(np.all(log.tickets['status'] == 1)) if log is not None and log.tickets is not None else None
+    if args.dump_outputs:
+        if log is not None:
+            tickets = log.tickets
+        else:
+            tickets = d_tick.download(TICKET_DTYPE) if deli is not None else None
+        dump_outputs(args.dump_outputs, eng, cs_fed, tickets, rank, world)
+        del tickets
 
-    # the HBM-resident figure (side field): the same steps with the log generated in HBM
-    if args.hbm_only:
-        elapsed_hbm = elapsed
-    else:
-        step_hbm()
-        deli_ms = 0.0
-        elapsed_hbm = timed(step_hbm)[0]
+    cs = cs_fed
+    elapsed_hbm = elapsed if args.hbm_only else None
+    rcls = min_bytes = None
+    if args.full:
+        # the HBM-resident figure (side field): the same steps with the log generated in HBM
+        if not args.hbm_only:
+            step_hbm()
+            deli_ms = 0.0
+            elapsed_hbm = timed(step_hbm)[0]
 
-    # the dominant kernel's roofline: one more (untimed) step with the classes serialized, so each
-    # class kernel has the GPU to itself and its launch duration is its own (in the timed steps the
-    # classes of a tick overlap on separate streams, which stretches every launch)
-    rcls = cls
-    if os.environ.get('MTGPU_SERIAL') != '1':
-        eng.set_concurrent_classes(False)
-        step_hbm()
-        eng.set_concurrent_classes(True)
-        rcls = {cap: [ms, n, b] for cap, ms, n, b in eng.last_class_stats()}
+        # the dominant kernel's roofline: one more (untimed) step with the classes serialized, so each
+        # class kernel has the GPU to itself and its launch duration is its own (in the timed steps the
+        # classes of a tick overlap on separate streams, which stretches every launch)
+        rcls = cls
+        if os.environ.get('MTGPU_SERIAL') != '1':
+            eng.set_concurrent_classes(False)
+            step_hbm()
+            eng.set_concurrent_classes(True)
+            rcls = {cap: [ms, n, b] for cap, ms, n, b in eng.last_class_stats()}
 
-    cs = eng.checksums()
+        cs = eng.checksums()
+        # SURVEY.md §8(d)'s b = infinity figure (the minimal traffic of the job): every op record and its
+        # payload read once, each document's state read once (empty after the reset: its 80-byte scalar
+        # header) and written once (35 B per final segment + the header)
+        if log is not None:
+            pay_b = float(log.tick_payload[-1])
+        else:  # the mean payload per op from the first 512 documents' logs
+            samp = dev.to_host(0, min(n_docs, 512))
+            pay_b = float(samp.ops['payload_len'].astype(np.float64).sum()) * n_ops / max(1, samp.n_ops)
+            del samp
+        ops_b = n_ops * 32 + pay_b
+        min_bytes = ops_b + 35.0 * float(eng.seg_counts().astype(np.float64).sum()) + 2 * 80.0 * n_docs
+        assert np.array_equal(cs_fed, cs), 'the host-fed tick steps differ from the HBM-resident replay'
     errs = sum(1 for d in range(0, n_docs, max(1, n_docs // 64)) if eng.error(d)[0])
-    # SURVEY.md §8(d)'s b = infinity figure (the minimal traffic of the job): every op record and its
-    # payload read once, each document's state read once (empty after the reset: its 80-byte scalar
-    # header) and written once (35 B per final segment + the header)
-    if log is not None:
-        pay_b = float(log.tick_payload[-1])
-    else:  # the mean payload per op from the first 512 documents' logs
-        samp = dev.to_host(0, min(n_docs, 512))
-        pay_b = float(samp.ops['payload_len'].astype(np.float64).sum()) * n_ops / max(1, samp.n_ops)
-        del samp
-    ops_b = n_ops * 32 + pay_b
-    min_bytes = ops_b + 35.0 * float(eng.seg_counts().astype(np.float64).sum()) + 2 * 80.0 * n_docs
-    assert np.array_equal(cs_fed, cs), 'the host-fed tick steps differ from the HBM-resident replay'
     if deli is None:
         assert np.array_equal(cs, gen_cs), 'replay does not reproduce the generation state'
     else:
         if ref_cs is not None:
             assert np.array_equal(cs, ref_cs), 'deli + apply is not deterministic across steps'
-        t = d_tick.download(TICKET_DTYPE)
-        assert np.all(t['status'] == 1), 'deli nacked or dropped a message of the synthetic stream'
+        if args.full or args.hbm_only:
+            t = d_tick.download(TICKET_DTYPE)
+            assert np.all(t['status'] == 1), 'deli nacked or dropped a message of the synthetic stream'
         assert tk_ok is not False, 'a ticket of the host-fed steps is not SENT'
     upload = None if log is None else {
               'bytes_per_step': log.upload_bytes(), 'ticks': log.n_ticks, 'first_tick_ops_per_doc': first_tick or args.ops_per_launch,
@@ -366,20 +387,22 @@ def main():
 
     total_ops = n_total * ops_per_doc * args.steps
     value = total_ops / elapsed
-    dom = max(rcls, key=lambda c: rcls[c][0])  # the capacity class with the most device time
-    d_ms, d_n, d_b = rcls[dom]
-    avg_launch_ms = d_ms / max(1, d_n)
-    bytes_per_launch = d_b / max(1, d_n)
-    achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if d_n else 0.0
-    all_achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else 0.0
+    if args.full:
+        dom = max(rcls, key=lambda c: rcls[c][0])  # the capacity class with the most device time
+        d_ms, d_n, d_b = rcls[dom]
+        avg_launch_ms = d_ms / max(1, d_n)
+        bytes_per_launch = d_b / max(1, d_n)
+        achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if d_n else 0.0
+        all_achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else 0.0
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline(dev, cs, n_docs, args.cpu_seconds, args.config)
 
-    kname_of = {c: eng.class_kernel(c) for c in rcls}
+    kname_of = {c: eng.class_kernel(c) for c in rcls} if args.full else None
     slow = None
-    if world == 1 and args.config == 'C3' and not args.no_slow_paths and not args.docs and not args.ops:
+    if (args.full and world == 1 and args.config == 'C3' and not args.no_slow_paths and not args.docs
+            and not args.ops):
         # the main engine's HBM goes back before the side lines allocate theirs
         kname_main = eng.class_kernel(max(rcls, key=lambda c: rcls[c][0]))
         dev.free()
@@ -387,7 +410,7 @@ def main():
         slow = slow_paths(device, docs_per_gpu, args.seed)
 
     if rank == 0:
-        kname = kname_main if slow is not None else eng.class_kernel(dom)
+        kname = (kname_main if slow is not None else eng.class_kernel(dom)) if args.full else None
         line = {
             'metric': METRIC,
             'value': round(value, 1),
@@ -396,6 +419,7 @@ def main():
             'steps': args.steps,
             'warmup': args.warmup,
             'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+            'apply_launches': launches,  # kernel launches the engine counted over the timed steps (rank 0)
             'higher_is_better': True,
             'scaling': 'weak',
             'vs_baseline': None,
@@ -415,7 +439,8 @@ def main():
                 'parallelism': f'hash-routed docs x{world} (splitmix64(docId) mod {world}; no collective in apply)',
                 'comm': type(comm).__name__,
             },
-            'roofline': {
+            'full': args.full,
+            'roofline': None if not args.full else {
                 'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic(kname, args.config),
                 'traffic_source': os.path.relpath(pmc_path(args.config), HERE) + ' (bytes per launch)',
@@ -437,17 +462,18 @@ def main():
                                       'classes_concurrent': os.environ.get('MTGPU_SERIAL') != '1',
                                       'kernel_share_of_step': round(kern_ms / (elapsed * 1e3), 3)},
             },
-            'deli': None if deli is None else {
+            'deli': None if deli is None or not args.full else {
                 'messages_per_step': n_msgs, 'joins_per_doc': n_join,
                 'kernel_ms_per_step': round(deli_ms / args.steps, 3),
                 'tickets_per_s_kernel': round(n_msgs / (deli_ms / args.steps * 1e-3), 1) if deli_ms else None,
                 'share_of_step': round(deli_ms / (elapsed_hbm * 1e3), 4),
                 'note': 'kernel time from the HBM-resident steps (in the host-fed steps deli runs per tick on the '
                         'engine stream)'},
-            'value_hbm_resident': {'value': round(total_ops / elapsed_hbm, 1), 'unit': 'ops/s',
-                                   'ms_per_step': round(elapsed_hbm / args.steps * 1e3, 3),
-                                   'note': 'the same steps with the op log already resident in HBM (generated '
-                                           'there): reset + apply' + (' (+ deli ticketing)' if deli is not None else '')},
+            'value_hbm_resident': None if not args.full else {
+                'value': round(total_ops / elapsed_hbm, 1), 'unit': 'ops/s',
+                'ms_per_step': round(elapsed_hbm / args.steps * 1e3, 3),
+                'note': 'the same steps with the op log already resident in HBM (generated there): reset + apply'
+                        + (' (+ deli ticketing)' if deli is not None else '')},
             'upload': upload,
             'slow_paths': slow,
             'cpu_baseline': cpu,
@@ -458,6 +484,50 @@ def main():
         }
         print(json.dumps(line), flush=True)
     comm.close()
+
+
+DUMP_SAMPLE_DOCS = 256          # documents whose length and error are read back one by one
+DUMP_MAX_DOCS = 1 << 20         # documents with per-document rows, over all ranks (32 B each: 32 MiB)
+DUMP_SAMPLE_TICKETS = 1 << 19   # tickets kept of a C5 step's, over all ranks (40 B each: 20 MiB)
+
+
+def dump_outputs(out_dir, eng, checksums, tickets, rank=0, world=1):
+    """--dump-outputs: what the last timed step left for its caller, as float64 <name>.npy files
+    (rank r of several writes <name>.rank<r>.npy).  The inputs are fixed by the arguments, so two
+    builds can be compared file by file:
+      doc_index     (n,)    the documents the next two describe, ascending: all of the rank's, or past
+                            DUMP_MAX_DOCS / ranks of them a fixed seeded sample of that size
+      checksums     (n, 2)  their 64-bit state checksums as (high, low) 32-bit halves
+      seg_counts    (n,)    segments each of them holds
+      sample_docs   (k,)    a fixed seeded sample of DUMP_SAMPLE_DOCS documents, ascending
+      sample_length (k,)    their getLength
+      sample_error  (k, 2)  their (error code, sequence number of the failing op); (0, 0): none
+      sample_ticket_index (m,), sample_tickets (m, 4)  C5 only: the step's deli tickets, (seq, msn,
+                            refSeq, status) each: all of them, or past DUMP_SAMPLE_TICKETS / ranks a
+                            fixed seeded sample of that size
+    The caps keep a dump below 64 MB in all, whatever --docs and --gpus are."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f'.rank{rank}' if world > 1 else ''
+    rng = np.random.default_rng(0x6D74)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + sfx + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+    def pick(n, cap):  # all of range(n), or a sorted sample of `cap` of them
+        return np.arange(n) if n <= cap else np.sort(rng.choice(n, size=cap, replace=False))
+    rows = pick(eng.n_docs, max(1, DUMP_MAX_DOCS // world))
+    save('doc_index', rows)
+    save('checksums', np.stack([checksums >> np.uint64(32), checksums & np.uint64(0xFFFFFFFF)], axis=1)[rows])
+    save('seg_counts', eng.seg_counts()[rows])
+    docs = pick(eng.n_docs, DUMP_SAMPLE_DOCS)
+    save('sample_docs', docs)
+    save('sample_length', [eng.length(int(d)) for d in docs])
+    save('sample_error', [eng.error(int(d)) for d in docs])
+    if tickets is not None:
+        idx = pick(len(tickets), max(1, DUMP_SAMPLE_TICKETS // world))
+        t = tickets[idx]
+        save('sample_ticket_index', idx)
+        save('sample_tickets', np.stack([t['seq'], t['msn'], t['ref_seq'], t['status']], axis=1))
 
 
 MT_CLASS_EDITING = 0x40000000  # include/mtgpu.h: the editing documents' bucket in the class stats

@@ -14,7 +14,7 @@ for cfg in ${CONFIGS:-C5}; do
   for lib in $LIBS; do
     n=$(basename $lib .so)
     for c in FETCH_SIZE WRITE_SIZE; do
-      MTGPU_LIB=$PWD/$lib MTGPU_SERIAL=1 timeout -s KILL 300 rocprofv3 --pmc $c -d $OUT/${cfg}_${n}_$c -o p -- python3 bench.py --config $cfg --steps 1 --warmup 0 --no-cpu-baseline --no-slow-paths --hbm-only > $OUT/${cfg}_${n}_$c.json 2> $OUT/${cfg}_${n}_$c.err || { tail -5 $OUT/${cfg}_${n}_$c.err; exit 1; }
+      MTGPU_LIB=$PWD/$lib MTGPU_SERIAL=1 timeout -s KILL 300 rocprofv3 --pmc $c -d $OUT/${cfg}_${n}_$c -o p -- python3 bench.py --full --config $cfg --steps 1 --warmup 0 --no-cpu-baseline --no-slow-paths --hbm-only > $OUT/${cfg}_${n}_$c.json 2> $OUT/${cfg}_${n}_$c.err || { tail -5 $OUT/${cfg}_${n}_$c.err; exit 1; }
     done
     python3 tools/pmc_traffic.py $OUT/${cfg}_${n}_FETCH_SIZE/p_results.db $OUT/${cfg}_${n}_WRITE_SIZE/p_results.db $OUT/${cfg}_${n}_pmc.json || exit 1
     rm -rf $OUT/${cfg}_${n}_FETCH_SIZE $OUT/${cfg}_${n}_WRITE_SIZE

@@ -26,7 +26,9 @@ if [ -z "$NO_SQ" ]; then
   rm -rf gpurun_out/sq
   echo "sq done"
 fi
-STEPS="${BENCHES:-bench c4 c5}" bash tools/gpu_check.sh > gpurun_out/r5f/benches.log 2>&1 || { tail -20 gpurun_out/r5f/benches.log; exit 1; }
-cp gpurun_out/bench_c3.json gpurun_out/bench_c4.json gpurun_out/bench_c5.json gpurun_out/r5f/ || exit 1
-cat gpurun_out/r5f/benches.log | cut -c1-600
+export OUT=${OUT:-bench_out}   # the bench lines (tools/gpu_check.sh: bench_<config>.json) and their log stay here
+mkdir -p $OUT
+STEPS="${BENCHES:-bench c4 c5}" bash tools/gpu_check.sh > $OUT/benches.log 2>&1 || { tail -20 $OUT/benches.log; exit 1; }
+for c in ${BENCHES:-bench c4 c5}; do [ -s $OUT/bench_${c/bench/c3}.json ] || { echo "no bench line for $c"; exit 1; }; done
+cut -c1-600 $OUT/benches.log
 echo evidence done

@@ -26,8 +26,9 @@ if [ "${PART:-A}" = A ]; then
   echo "part A done"
 else
   for c in ${PROF_CONFIGS:-C4 C5}; do prof $c "" || exit 1; done
-  STEPS="${BENCHES:-bench c4 c5}" bash tools/gpu_check.sh > gpurun_out/r6f/benches.log 2>&1 || { tail -20 gpurun_out/r6f/benches.log; exit 1; }
-  for f in bench_c3.json bench_c4.json bench_c5.json; do [ -f gpurun_out/$f ] && cp gpurun_out/$f gpurun_out/r6f/; done
-  cut -c1-600 gpurun_out/r6f/benches.log
+  export OUT=${OUT:-bench_out}   # the bench lines (tools/gpu_check.sh: bench_<config>.json) and their log stay here
+  mkdir -p $OUT
+  STEPS="${BENCHES:-bench c4 c5}" bash tools/gpu_check.sh > $OUT/benches.log 2>&1 || { tail -20 $OUT/benches.log; exit 1; }
+  cut -c1-600 $OUT/benches.log
   echo "part B done"
 fi

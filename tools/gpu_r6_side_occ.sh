@@ -13,7 +13,7 @@ if [ -n "${C64_LIBS-ablib/libmtgpu_hd.so ablib/libmtgpu_c64a.so ablib/libmtgpu_c
 fi
 for rep in 1 2; do
   for v in ${EV_VARIANTS:-hd ev8 ev8910}; do
-    MTGPU_LIB=$PWD/ablib/libmtgpu_$v.so timeout -k 10 300 python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/ev_${v}_$rep.json 2> $OUT/ev_${v}_$rep.err || { tail -20 $OUT/ev_${v}_$rep.err; exit 1; }
+    MTGPU_LIB=$PWD/ablib/libmtgpu_$v.so timeout -k 10 300 python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/ev_${v}_$rep.json 2> $OUT/ev_${v}_$rep.err || { tail -20 $OUT/ev_${v}_$rep.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1]))['slow_paths']['C3_events']; print(sys.argv[1], round(d['value']/1e6,2), d['roofline']['class_ms_serialized'], d['parity'])" $OUT/ev_${v}_$rep.json
   done
 done

@@ -8,11 +8,13 @@ mkdir -p gpurun_out
 STEPS="tests" bash tools/gpu_check.sh || exit 1
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -20 gpurun_out/smoke.log; exit 1; }
 tail -1 gpurun_out/smoke.log
-STEPS="bench c4 c5" bash tools/gpu_check.sh > gpurun_out/bench_lines.log 2>&1 || { tail -20 gpurun_out/bench_lines.log; exit 1; }
+export OUT=${OUT:-bench_out}   # tools/gpu_check.sh writes bench_<config>.json here; read below
+mkdir -p $OUT
+STEPS="bench c4 c5" bash tools/gpu_check.sh > $OUT/bench_lines.log 2>&1 || { tail -20 $OUT/bench_lines.log; exit 1; }
 python3 -c "
-import json
+import json, os
 for c in ('c3', 'c4', 'c5'):
-    d = json.load(open('gpurun_out/bench_%s.json' % c))
+    d = json.load(open(os.path.join(os.environ['OUT'], 'bench_%s.json' % c)))
     cb = d.get('cpu_baseline') or {}
     print(c, d['value'], d['roofline']['kernel'], d['roofline']['frac'], (d.get('value_with_h2d') or {}).get('value'), cb.get('value'), cb.get('reference_estimate'), d.get('parity'))
 "

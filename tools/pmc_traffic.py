@@ -47,7 +47,7 @@ def main():
         w = sum(write.get(k, [])) / max(1, len(write.get(k, [])))
         out[short_name(k)] = {'mangled': k, 'fetch_bytes_per_launch_raw': f, 'write_bytes_per_launch': w,
                   'hbm_bytes_per_launch': 2.0 * f + w, 'launches': len(fetch.get(k, []))}
-    meta = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `bench.py --steps 1 --warmup 0 '
+    meta = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `bench.py --full --steps 1 --warmup 0 '
                       '--no-cpu-baseline` (tools/rocprof.sh)',
             'correction': 'hbm_bytes = 2 x FETCH_SIZE + WRITE_SIZE (gfx950 FETCH_SIZE counts half of wide reads)',
             'kernels': out}
