@@ -487,6 +487,28 @@ struct Wave {
         }
         sync();
         if (cnt == 0) return emit(is_remove ? MT_EV_REMOVE : MT_EV_ANNOTATE, MT_EVF_FIRST | MT_EVF_EMPTY, -1, -1, 0);
+        if (is_remove && (s.wide & MT_WIDE_REFS)) {
+            // A document that holds local references: where the removed segments' references slide
+            // (markRangeRemoved, mergeTree.ts:2671-2696), into the callback's first record.  cum is
+            // still the remover's view from before the marks, and the marks hid exactly its spans
+            // inside [start, end): in the view after them getContainingSegment(start) is the first
+            // leaf past the range with a span (the `before` form), and, when there is none,
+            // getContainingSegment(length - 1) the last leaf with a span before `start` (`after`).
+            int tb = INT32_MAX, ta = -1;
+            for (int i = lane; i < n; i += 64) {
+                const int ce = s.cum[i], cs = cstart(i);
+                if (ce > cs) {
+                    if (cs >= end) tb = min(tb, i);
+                    if (ce <= start) ta = max(ta, i);
+                }
+            }
+            tb = wave_min(tb);
+            ta = wave_max(ta);
+            const int t = tb != INT32_MAX ? tb : ta;
+            if (lane == 0 && t >= 0 && e0 < (int)evcap)
+                ev[e0].pad2 = (uint64_t)(uint32_t)(t + 1) | ((uint64_t)(s.len[s.order[t]] & 0x7FFFFFFFu) << 32) |
+                              (tb != INT32_MAX ? 0ull : 1ull << 63);
+        }
         s.evn = e0 + cnt;
         sync();
     }

@@ -66,6 +66,15 @@ extern "C" hipError_t mt_launch_seginfo(const mt_gstate* g, const uint32_t* docs
                                         mt_seg_info* out, hipStream_t st);
 extern "C" hipError_t mt_launch_events_pack(const mt_gstate* g, uint32_t n_docs, const uint64_t* off, mt_event* out,
                                             hipStream_t st);
+extern "C" hipError_t mt_launch_refs_track(const mt_gstate* g, uint32_t n_docs, hipStream_t st);
+extern "C" hipError_t mt_launch_refs_claim(const mt_gstate* g, const mt_ref_add* in, const mt_pos_result* at, uint32_t n,
+                                           uint32_t n_docs, uint32_t* handles, hipStream_t st);
+extern "C" hipError_t mt_launch_refs_release(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
+                                             uint32_t n_docs, hipStream_t st);
+extern "C" hipError_t mt_launch_refs_free_docs(const mt_gstate* g, const uint32_t* ids, uint32_t n, uint32_t n_docs,
+                                               hipStream_t st);
+extern "C" hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
+                                               uint32_t n_docs, mt_ref_pos* out, hipStream_t st);
 extern "C" hipError_t mt_launch_fixup(const mt_gstate* g, const mt_op_rec* ops, uint32_t n_docs, hipStream_t st);
 extern "C" hipError_t mt_launch_scan_records(const mt_op_rec* ops, uint64_t n_ops, uint64_t payload_bytes,
                                              uint32_t* flags, hipStream_t st);
@@ -520,6 +529,28 @@ mt_status mt_engine_create(const mt_cfg* cfg, mt_engine** out) {
     return MT_OK;
 }
 
+// the local-reference tables (mt_refs_enable)
+static void refs_free(mt_engine* e) {
+    for (void* p : {(void*)e->g.refs, (void*)e->g.refpos, (void*)e->g.refcur, (void*)e->g.refn, (void*)e->g.refq,
+                    (void*)e->g.refdrop})
+        if (p) (void)hipFree(p);
+    e->g.refs = nullptr;
+    e->g.refpos = nullptr;
+    e->g.refcur = e->g.refn = e->g.refq = e->g.refdrop = nullptr;
+    e->g.refcap = 0;
+}
+// every document's references freed, cursors at the start of the event buffer
+static hipError_t refs_clear(mt_engine* e) {
+    if (!e->g.refs) return hipSuccess;
+    const size_t D = e->cfg.max_docs;
+    hipError_t r = hipMemsetAsync(e->g.refs, 0, D * 2 * e->g.refcap * sizeof(mt_ref), e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(e->g.refcur, 0, D * sizeof(uint32_t), e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(e->g.refn, 0, D * sizeof(uint32_t), e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(e->g.refq, 0, D * sizeof(uint32_t), e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(e->g.refdrop, 0, D * sizeof(uint32_t), e->stream);
+    return r;
+}
+
 mt_status mt_engine_destroy(mt_engine* e) {
     if (!e) return MT_ERR_ARG;
     hipSetDevice(e->cfg.device);
@@ -527,6 +558,7 @@ mt_status mt_engine_destroy(mt_engine* e) {
     for (void* p : e->allocs) hipFree(p);
     if (e->g.ev) (void)hipFree(e->g.ev);
     if (e->g.evn) (void)hipFree(e->g.evn);
+    refs_free(e);
     if (e->ws) (void)hipFree(e->ws);
     for (void* p : {(void*)e->g.gmb, (void*)e->g.pkb, (void*)e->g.ctb, (void*)e->g.lsqb, (void*)e->g.gmx,
                     (void*)e->g.locx})
@@ -585,6 +617,7 @@ mt_status mt_docs_init(mt_engine* e, uint32_t n_docs) {
         e->free_gx.clear();
     }
     HIP_OK(mt_launch_init(&e->g, n_docs, e->stream));
+    HIP_OK(refs_clear(e));  // (rows still in the event buffer: the next fold only moves the cursors past them)
     HIP_OK(hipStreamSynchronize(e->stream));
     return MT_OK;
 }
@@ -676,6 +709,7 @@ mt_status mt_docs_load(mt_engine* e, uint32_t n, const uint32_t* doc_ids, const 
         if (mt_launch_load(&e->g, n, reinterpret_cast<uint32_t*>(buf + o_ids), reinterpret_cast<uint32_t*>(buf + o_rp),
                            reinterpret_cast<mt_load_seg*>(buf + o_sg), buf + o_tx, reinterpret_cast<int32_t*>(buf + o_mn),
                            reinterpret_cast<int32_t*>(buf + o_cs), e->stream) != hipSuccess ||
+            mt_launch_refs_free_docs(&e->g, reinterpret_cast<uint32_t*>(buf + o_ids), n, e->n_docs, e->stream) != hipSuccess ||
             hipStreamSynchronize(e->stream) != hipSuccess)
             st = MT_ERR_HIP;
     } while (0);
@@ -822,6 +856,7 @@ mt_status mt_events_enable(mt_engine* e, uint32_t per_doc) {
     HIP_OK(hipStreamSynchronize(e->stream));
     if (e->g.ev) HIP_OK(hipFree(e->g.ev));
     if (e->g.evn) HIP_OK(hipFree(e->g.evn));
+    refs_free(e);  // (they follow this buffer's rows)
     e->g.ev = nullptr;
     e->g.evn = nullptr;
     e->g.evcap = 0;
@@ -849,6 +884,7 @@ mt_status mt_events_enable(mt_engine* e, uint32_t per_doc) {
 mt_status mt_events_drain(mt_engine* e, mt_event* out, uint64_t cap, uint32_t* row_ptr, uint64_t* total) {
     if (!e || !row_ptr || !total || !e->g.ev) return MT_ERR_ARG;
     HIP_OK(hipSetDevice(e->cfg.device));
+    if (out) HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));  // the rows move the references first
     HIP_OK(hipStreamSynchronize(e->stream));
     const uint32_t n = e->n_docs;
     std::vector<uint32_t> cnt(n);
@@ -879,8 +915,121 @@ mt_status mt_events_drain(mt_engine* e, mt_event* out, uint64_t cap, uint32_t* r
         if (st) return st;
     }
     HIP_OK(hipMemsetAsync(e->g.evn, 0, (size_t)n * sizeof(uint32_t), e->stream));
+    if (e->g.refcur) HIP_OK(hipMemsetAsync(e->g.refcur, 0, (size_t)n * sizeof(uint32_t), e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));
     return MT_OK;
+}
+
+// ---- local references (include/mtgpu.h; kernels in mt_refs.hip) ---------------------------------
+mt_status mt_refs_enable(mt_engine* e, uint32_t per_doc) {
+    static_assert(sizeof(mt_ref) == 16 && sizeof(mt_ref_add) == 12 && sizeof(mt_ref_pos) == 12, "reference records");
+    if (!e || (per_doc && !e->g.ev) || per_doc > MT_REFS_MAX) return MT_ERR_ARG;  // (the fold stages a table in LDS)
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    refs_free(e);
+    if (!per_doc) return MT_OK;
+    const size_t D = e->cfg.max_docs;
+    if (hipMalloc(&e->g.refs, D * 2 * per_doc * sizeof(mt_ref)) != hipSuccess ||
+        hipMalloc(&e->g.refpos, D * per_doc * sizeof(mt_ref_pos)) != hipSuccess ||
+        hipMalloc(&e->g.refcur, D * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&e->g.refn, D * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&e->g.refq, D * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&e->g.refdrop, D * sizeof(uint32_t)) != hipSuccess) {
+        refs_free(e);
+        return MT_ERR_NOMEM;
+    }
+    e->g.refcap = per_doc;
+    HIP_OK(refs_clear(e));
+    // (rows recorded before now concern no reference: the first fold only moves the cursors past them)
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return MT_OK;
+}
+
+mt_status mt_refs_add(mt_engine* e, const mt_ref_add* in, uint32_t n, uint32_t* handles) {
+    if (!e || !e->g.refs || (n && (!in || !handles))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (in[i].doc >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    if (n == 0) return MT_OK;
+    e->gen++;
+    std::vector<mt_pos_query> q(n);
+    for (uint32_t i = 0; i < n; i++) q[i] = mt_pos_query{in[i].doc, in[i].pos, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
+    void* buf = nullptr;
+    const size_t ab = (size_t)n * sizeof(mt_ref_add), qb = (size_t)n * sizeof(mt_pos_query),
+                 rb = (size_t)n * sizeof(mt_pos_result), hb = (size_t)n * sizeof(uint32_t);
+    const size_t o_q = (ab + 15) & ~size_t(15), o_r = o_q + qb, o_h = o_r + rb;
+    if (hipMalloc(&buf, o_h + hb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* b8 = static_cast<uint8_t*>(buf);
+    auto* da = reinterpret_cast<mt_ref_add*>(b8);
+    auto* dq = reinterpret_cast<mt_pos_query*>(b8 + o_q);
+    auto* dr = reinterpret_cast<mt_pos_result*>(b8 + o_r);
+    auto* dh = reinterpret_cast<uint32_t*>(b8 + o_h);
+    hipError_t r = hipMemcpyAsync(da, in, ab, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(dq, q.data(), qb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_resolve(&e->g, dq, n, e->n_docs, dr, e->stream);
+    if (r == hipSuccess) r = mt_launch_refs_claim(&e->g, da, dr, n, e->n_docs, dh, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(handles, dh, hb, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+}
+
+mt_status mt_refs_remove(mt_engine* e, const uint32_t* docs, const uint32_t* handles, uint32_t n) {
+    if (!e || !e->g.refs || (n && (!docs || !handles))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    if (n == 0) return MT_OK;
+    uint32_t* buf = nullptr;
+    const size_t nb = (size_t)n * sizeof(uint32_t);
+    if (hipMalloc(&buf, 2 * nb) != hipSuccess) return MT_ERR_NOMEM;
+    hipError_t r = hipMemcpyAsync(buf, docs, nb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(buf + n, handles, nb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_refs_release(&e->g, buf, buf + n, n, e->n_docs, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+}
+
+mt_status mt_refs_dropped(mt_engine* e, uint32_t* out, uint32_t n_docs) {
+    if (!e || !e->g.refs || !out || n_docs > e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (n_docs) HIP_OK(hipMemcpy(out, e->g.refdrop, (size_t)n_docs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MT_OK;
+}
+
+mt_status mt_refs_positions_device(mt_engine* e, const uint32_t* d_docs, const uint32_t* d_handles, uint32_t n,
+                                   mt_ref_pos* d_out) {
+    if (!e || !e->g.refs || (n && (!d_docs || !d_handles || !d_out))) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    HIP_OK(mt_launch_refs_positions(&e->g, d_docs, d_handles, n, e->n_docs, d_out, e->stream));
+    return MT_OK;
+}
+
+mt_status mt_refs_positions(mt_engine* e, const uint32_t* docs, const uint32_t* handles, uint32_t n, mt_ref_pos* out) {
+    if (!e || !e->g.refs || (n && (!docs || !handles || !out))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    if (n == 0) return mt_refs_positions_device(e, nullptr, nullptr, 0, nullptr);
+    uint8_t* buf = nullptr;
+    const size_t nb = (size_t)n * sizeof(uint32_t), ob = (size_t)n * sizeof(mt_ref_pos);
+    if (hipMalloc(&buf, 2 * nb + ob) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dd = reinterpret_cast<uint32_t*>(buf);
+    auto* dout = reinterpret_cast<mt_ref_pos*>(buf + 2 * nb);
+    hipError_t r = hipMemcpyAsync(dd, docs, nb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(dd + n, handles, nb, hipMemcpyHostToDevice, e->stream);
+    mt_status st = MT_OK;
+    if (r == hipSuccess) st = mt_refs_positions_device(e, dd, dd + n, n, dout);
+    if (r == hipSuccess && st == MT_OK) r = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r != hipSuccess ? MT_ERR_HIP : st;
 }
 
 mt_status mt_batch_upload(mt_engine* e, const mt_op_rec* ops, uint64_t n_ops, const uint8_t* payload,

@@ -55,6 +55,8 @@ struct mt_doc_scalars {      // 84 bytes
 #define MT_WIDE_C64 4u  // has seen a client id above 32: 64-bit overlap sets (register engine: its C64 form)
 #define MT_WIDE_GROUPS 8u  // an editing document past 64 pending edits at once: the editing form with
                            // MT_LOC_GROUPS_WIDE group slots (its HBM-workspace form), for good
+#define MT_WIDE_REFS 256u  // holds (or has held) local references (mt_refs_add), for good: set together with
+                           // MT_WIDE_LDS; its REMOVE callbacks record the slide target (mt_apply.hip emit_range)
 // The wide form's extension: property keys 16..31 (pxx) and overlapping removers >= 64 past the 16th
 // per segment (ovx words 4..7).  It never takes LDS: a launch stages it in an HBM workspace region
 // per document (the LDS-staged classes) or in the document's HBM workspace (the others), and only
@@ -103,6 +105,33 @@ struct mt_locx {
 // 7 bits per key id 0..7 at bit 7k, the pending rewrite count in bits 56..63
 #define MT_PK_KEY(pk, k) ((uint32_t)((pk) >> (7 * (k))) & 0x7Fu)
 #define MT_PK_RW(pk) ((uint32_t)((pk) >> 56))
+
+// One entry of a document's local-reference table: a LocalReference (localReference.ts:20-119) as the
+// segment it sits on -- its ordinal among the linked leaves, -1: detached -- and its offset there.
+// The table has 2 * refcap entries: references in the first half (a handle is its index), and in the
+// second "ghosts": a segment's LocalReferenceCollection that holds no reference any more but still
+// exists, with its refsByOffset.length.  That length (rlen; every entry of one segment carries the
+// same) is what LocalReferenceCollection.append adds to the offsets it moves (localReference.ts:277),
+// and the reference lets it go stale: append returns early for an empty `other` (:269-271) and split
+// skips an empty collection (:284), so it need not equal the segment's cachedLength.
+struct mt_ref {              // 16 bytes
+    int32_t ord;
+    uint32_t off;
+    uint32_t flags;          // 0: a free entry; else MT_RF_LIVE | the refType's low 16 bits | MT_RF_*
+    uint32_t rlen;           // refsByOffset.length of the segment's collection (pending: its cachedLength)
+};
+#define MT_RF_TYPE 0xFFFFu       // refType (ops.ts:6-16; SlideOnRemove 0x40)
+#define MT_RF_BEFORE 0x10000u    // the list of its IRefsAtOffest it sits in (localReference.ts:121-125): neither
+#define MT_RF_AFTER 0x20000u     // bit: `at`
+#define MT_RF_LOOSE 0x40000u     // left on its removed segment by LocalReferenceCollection.clear(), which skips
+                                 // the `after` lists (localReference.ts:198-204): in no collection any more, so a
+                                 // split leaves it on the first half; detached when the segment is unlinked
+#define MT_RF_PENDING 0x10000000u  // (with LIVE) added since the last fold: joins its segment's collection there
+#define MT_RF_ZOMBIE 0x20000000u   // removed since the last fold: becomes a ghost there if it was the last one
+#define MT_RF_GHOST 0x40000000u
+#define MT_RF_LIVE 0x80000000u
+#define MT_REFQ_ASKED 1u         // mt_gstate.refq bits: queried by the mt_refs_positions call in flight;
+#define MT_REFQ_DIRTY 2u         // pending or zombie entries to settle
 
 // Device pointers + capacities (one allocation per array, [n_docs][capacity]).
 struct mt_gstate {
@@ -166,5 +195,12 @@ struct mt_gstate {
     uint32_t* locgx;   // [doc]
     struct mt_op_rec* rg;  // [doc][MT_RG_RECS] regenerated ops (seq = the resetting record's index)
     uint8_t* rgp;      // [doc][MT_RG_BYTES] their payload
-    uint32_t segcap, lbcap, ibcap, hcap, textcap, evcap;
+    // local references (mt_refs_enable; null when off), [doc][refcap] and [doc]
+    mt_ref* refs;      // [doc][2 * refcap]
+    struct mt_ref_pos* refpos;  // [doc][refcap] each entry's answer at the document's last resolve
+    uint32_t* refcur;  // [doc] event rows of the document already folded into its references
+    uint32_t* refn;    // [doc] entries in use (references and ghosts)
+    uint32_t* refq;    // [doc] MT_REFQ_*
+    uint32_t* refdrop; // [doc] ghosts dropped for want of room (mt_refs_dropped)
+    uint32_t segcap, lbcap, ibcap, hcap, textcap, evcap, refcap;
 };

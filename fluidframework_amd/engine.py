@@ -108,6 +108,11 @@ def lib():
         L.mt_events_enable.argtypes = [vp, u32]
         L.mt_events_drain.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64)]
         L.mt_set_label_keys.argtypes = [vp, u32, i32, i32]
+        for name, at in (('mt_refs_enable', [vp, u32]), ('mt_refs_add', [vp, vp, u32, vp]),
+                         ('mt_refs_remove', [vp, vp, vp, u32]), ('mt_refs_positions', [vp, vp, vp, u32, vp]),
+                         ('mt_refs_positions_device', [vp, vp, vp, u32, vp]), ('mt_refs_dropped', [vp, vp, u32])):
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ctypes.c_int
         L.mt_version.restype = ctypes.c_char_p
         for name in ('mt_engine_create', 'mt_engine_destroy', 'mt_docs_init', 'mt_batch_upload', 'mt_batch_apply',
                      'mt_batch_free', 'mt_submit', 'mt_sync', 'mt_get_length', 'mt_get_text', 'mt_get_state',
@@ -366,6 +371,53 @@ class MergeEngine:
         from .events import callbacks
         rows, rp = self.drain_event_rows()
         return [callbacks(rows[rp[d]:rp[d + 1]]) for d in range(self.n_docs)]
+
+    # -- local references (localReference.ts; include/mtgpu.h) --------------------------------
+    def enable_refs(self, per_doc=64):
+        """Room for `per_doc` local references per document (0 frees them).  Needs enable_events():
+        the references follow the recorded callbacks."""
+        _check(lib().mt_refs_enable(self.h, per_doc), 'mt_refs_enable')
+        return self
+
+    def add_refs(self, docs, positions, ref_types):
+        """addLocalReference at getContainingSegment(pos) of each document's local view: one handle
+        per entry (refs.REF_NONE: pos outside the view; refs.REF_FULL: the document's table is full)."""
+        from .refs import REF_ADD_DTYPE
+        a = np.zeros(len(docs), dtype=REF_ADD_DTYPE)
+        a['doc'], a['pos'], a['ref_type'] = docs, positions, ref_types
+        out = np.zeros(len(a), dtype=np.uint32)
+        _check(lib().mt_refs_add(self.h, _ptr(a), len(a), _ptr(out)), 'mt_refs_add')
+        return out
+
+    def remove_refs(self, docs, handles):
+        """removeLocalReference for a batch of (document, handle) pairs."""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        h = np.ascontiguousarray(handles, dtype=np.uint32)
+        assert len(d) == len(h)
+        _check(lib().mt_refs_remove(self.h, _ptr(d), _ptr(h), len(d)), 'mt_refs_remove')
+
+    def ref_positions(self, docs, handles):
+        """refs.REF_POS_DTYPE rows (toPosition(), segment ordinal, getOffset()) of a batch of
+        (document, handle) pairs; a detached reference answers (-1, -1, 0)."""
+        from .refs import REF_POS_DTYPE
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        h = np.ascontiguousarray(handles, dtype=np.uint32)
+        assert len(d) == len(h)
+        out = np.zeros(len(d), dtype=REF_POS_DTYPE)
+        _check(lib().mt_refs_positions(self.h, _ptr(d), _ptr(h), len(d), _ptr(out)), 'mt_refs_positions')
+        return out
+
+    def refs_dropped(self):
+        """Per document, the collections without references its table had no room to keep
+        (mt_refs_dropped): 0 means every ref_positions answer is the reference's."""
+        out = np.zeros(self.n_docs, dtype=np.uint32)
+        _check(lib().mt_refs_dropped(self.h, _ptr(out), self.n_docs), 'mt_refs_dropped')
+        return out
+
+    def ref_positions_device(self, d_docs, d_handles, n, d_out):
+        """mt_refs_positions_device: device pointers (ints); complete after the sync done here."""
+        _check(lib().mt_refs_positions_device(self.h, d_docs, d_handles, n, d_out), 'mt_refs_positions_device')
+        _check(lib().mt_sync(self.h), 'mt_sync')
 
     # -- readout -------------------------------------------------------------------------
     def checksums(self):

@@ -493,7 +493,8 @@ typedef struct mt_event {   /* 96 bytes */
     uint32_t len;
     uint32_t pmask;         /* ANNOTATE: keys present in propertyDeltas (bit k = key id k)        */
     uint16_t pvals[MT_MAX_KEYS_WIDE]; /* ANNOTATE: previous value id of key k (0 = null)          */
-    uint64_t pad2;
+    uint64_t pad2;          /* first record of a REMOVE callback of a document that holds local
+                               references: MT_EVT_* (the slide target, see "local references"); else 0 */
 } mt_event;
 /* Start recording: `per_doc` records per document between drains (0 stops recording).  A
  * document that would exceed it halts with MT_DERR_EVENTS. */
@@ -502,6 +503,87 @@ mt_status mt_events_enable(mt_engine* eng, uint32_t per_doc);
  * records are out[row_ptr[d] .. row_ptr[d+1]) (row_ptr: n_docs + 1 entries).  With out == NULL
  * (or cap too small: MT_ERR_ARG) only row_ptr / *total are filled and nothing is cleared. */
 mt_status mt_events_drain(mt_engine* eng, mt_event* out, uint64_t cap, uint32_t* row_ptr, uint64_t* total);
+
+/* ---- local references -------------------------------------------------------
+ * LocalReference (packages/dds/merge-tree/src/localReference.ts:20-119): a (segment, offset) pair
+ * that follows the segment through edits -- what SharedString's interval collections, comments,
+ * cursors and undo anchors rest on (Client.addLocalReference / removeLocalReference,
+ * client.ts:294-300 -> mergeTree.ts:2728-2746).  The engine keeps `per_doc` of them per document on
+ * the device as (ordinal of the segment among the linked leaves, offset) and moves them exactly where
+ * the reference does, by folding the document's delta / maintenance events (above) in firing order:
+ *   SPLIT   BaseSegment.splitAt -> LocalReferenceCollection.split (mergeTree.ts:562-564,
+ *           localReference.ts:283-301): offsets >= the first half's length move to the second half;
+ *   APPEND  TextSegment.append -> LocalReferenceCollection.append (textSegment.ts:74-81,
+ *           localReference.ts:268-281): the second segment's references move onto the first;
+ *   UNLINK  zamboni drops the segment (mergeTree.ts:1310-1317): segment.parent is undefined and
+ *           toPosition() answers DetachedPosition (-1);
+ *   REMOVE  markRangeRemoved (mergeTree.ts:2639-2643, 2671-2696): the references of the segments this
+ *           op removed slide, if their refType has SlideOnRemove (ops.ts:13), to the start of the
+ *           segment holding `start` in the remover's view after the removal (addBeforeTombstones,
+ *           localReference.ts:303-331) or, when nothing follows, to the last character of the segment
+ *           before it (addAfterTombstones, :333-361); others are detached.  With no segment left in
+ *           that view LocalReferenceCollection.clear() runs (:186-206), which detaches the `before`
+ *           and `at` lists but names `before` twice: a reference in an `after` list stays on its
+ *           removed segment until zamboni unlinks it.  The engine does the same;
+ *   INSERT  only renumbers the leaves; ANNOTATE moves nothing.
+ * APPEND shifts the offsets it moves by the first segment's refsByOffset.length (localReference.ts:277),
+ * which the reference lets go stale -- append returns early for an empty `other` (:269-271), split
+ * skips an empty collection (:284) -- so it need not be the segment's length; the engine keeps that
+ * length per collection, also for a collection that outlives its references (per document as many
+ * such collections as references fit; one past that is forgotten and counted -- mt_refs_dropped -- and
+ * an append onto it then shifts by the segment's length: from a document's first dropped collection
+ * on its references may differ from the reference's).  One difference is kept: where a slide left refsByOffset[offset] without an
+ * `at` list the reference's addLocalRef throws (:212-219); mt_refs_add adds the reference.
+ * The fold is lazy: it runs at the start of mt_refs_add / mt_refs_remove / mt_refs_positions and of
+ * mt_events_drain, never inside an apply.  A document that halts keeps its references as of the
+ * events it recorded.  mt_docs_init and mt_docs_load free the documents' references.
+ * The slide target is known only to the apply: for a document that holds references the first
+ * record of each REMOVE callback carries it in mt_event.pad2 (0 for every other document):
+ *   bits 0..31 the target's leaf ordinal + 1 (0: none), bits 32..62 its cachedLength, bit 63 set for
+ *   the `after` form. */
+#define MT_EVT_ORDINAL(t) ((int32_t)((uint32_t)(t)) - 1)
+#define MT_EVT_LENGTH(t) ((uint32_t)(((t) >> 32) & 0x7FFFFFFFu))
+#define MT_EVT_AFTER(t) ((uint32_t)((t) >> 63))
+#define MT_REF_SLIDE_ON_REMOVE 0x40u /* ReferenceType.SlideOnRemove (ops.ts:13) */
+#define MT_REF_NONE 0xFFFFFFFFu      /* mt_refs_add: pos is outside the local view (no containing segment) */
+#define MT_REF_FULL 0xFFFFFFFEu      /* mt_refs_add: the document's table is full (the document goes on) */
+#define MT_REF_BAD_HANDLE (-2)       /* mt_refs_positions: ordinal of a handle that names no reference */
+typedef struct mt_ref_add {  /* 12 bytes */
+    uint32_t doc;
+    int32_t pos;             /* the reference sits at getContainingSegment(pos) of the local view */
+    uint32_t ref_type;       /* ReferenceType bits (ops.ts:6-16), low 16 bits */
+} mt_ref_add;
+typedef struct mt_ref_pos {  /* 12 bytes */
+    int32_t position;        /* LocalReference.toPosition(): getPosition(segment) + getOffset(), -1 detached */
+    int32_t ordinal;         /* the segment's index among the linked leaves, -1 detached */
+    uint32_t offset;         /* getOffset(): 0 on a removed segment (a pending local removal included) */
+} mt_ref_pos;
+#define MT_REFS_MAX 1024u             /* references per document (mt_refs_enable) */
+/* Allocate (0 < per_doc <= MT_REFS_MAX) or free (0) the reference tables.  MT_ERR_ARG unless mt_events_enable is on:
+ * the fold reads that buffer, so size it for the callbacks between two folds (a document past it halts
+ * with MT_DERR_EVENTS).  Event recording is engine-wide today, so enabling references makes every
+ * document record; recording per document is a follow-up.  mt_events_enable frees the tables. */
+mt_status mt_refs_enable(mt_engine* eng, uint32_t per_doc);
+/* new LocalReference(client, segment, offset, refType) + addLocalReference for a batch: handles[i]
+ * names in[i]'s reference within its document, or is MT_REF_NONE / MT_REF_FULL.  A document's first
+ * reference marks it, for good, as holding references: it runs on the LDS engine from then on (as
+ * with mt_set_label_keys) and its REMOVE callbacks carry slide targets. */
+mt_status mt_refs_add(mt_engine* eng, const mt_ref_add* in, uint32_t n, uint32_t* handles);
+/* removeLocalReference: the handles are free for reuse (one that names no reference is ignored) */
+mt_status mt_refs_remove(mt_engine* eng, const uint32_t* docs, const uint32_t* handles, uint32_t n);
+/* toPosition() / segment / getOffset() of a batch of references, one wave per queried document */
+mt_status mt_refs_positions(mt_engine* eng, const uint32_t* docs, const uint32_t* handles, uint32_t n, mt_ref_pos* out);
+/* the same with device-resident arguments and results (asynchronous on the engine's stream) */
+mt_status mt_refs_positions_device(mt_engine* eng, const uint32_t* d_docs, const uint32_t* d_handles, uint32_t n,
+                                   mt_ref_pos* d_out);
+
+/* out[d] = collections without references that document d's table had no room to keep (see above)
+ * since its references were last freed, for documents 0..n_docs-1; folds first.  0: every answer of
+ * mt_refs_positions is the reference's. */
+mt_status mt_refs_dropped(mt_engine* eng, uint32_t* out, uint32_t n_docs);
+/* Today every call above, and mt_events_drain, launches its fold and its resolve with one wave per
+ * document of the engine; the documents not involved leave at once.  Launching over a compacted
+ * list of the documents with references / queried is a follow-up. */
 
 /* ---- bench tooling (not part of the applyMsg boundary) -------------------------------------
  * Synthetic multi-client op streams (DESIGN.md "Synthetic workloads", after SURVEY.md §8d),

@@ -28,6 +28,7 @@
 const path = require("path");
 
 const native = require(path.join(__dirname, "mtgpu.node"));
+const { LocalReference, ReferenceType, REF_NONE, REF_FULL } = require(path.join(__dirname, "localReference.js"));
 
 const INSERT = 0, REMOVE = 1, ANNOTATE = 2, GROUP = 3, NOOP = 3;
 const F_REWRITE = 1, F_PROPS = 2, F_GROUP_MORE = 4, F_MARKER = 128;
@@ -60,6 +61,8 @@ class BatchEngine {
         this.pending = 0;
         this.recording = false;
         this.eventsPerDoc = opts.eventsPerDoc || (1 << 16);
+        this.refsOn = false;
+        this.refsPerDoc = opts.refsPerDoc || 64;  // local references per document (mt_refs_enable)
         this.labelDecl = [];  // [doc, tile key, range key] to declare before the next submit
         this.gen = 0;         // bumped by every submit: segment descriptors are valid within one generation
         this.syncCallbacks = !!opts.syncCallbacks;  // deliver callbacks before the firing call returns
@@ -71,6 +74,14 @@ class BatchEngine {
         this.flush();  // ops queued before the callback was set were "applied" before it
         native.eventsEnable(this.handle, this.eventsPerDoc);
         this.recording = true;
+    }
+
+    /** Local references follow the recorded callbacks (mt_refs_enable needs mt_events_enable). */
+    _enableRefs() {
+        if (this.refsOn) return;
+        this._enableEvents();
+        native.refsEnable(this.handle, this.refsPerDoc);
+        this.refsOn = true;
     }
 
     /** Deliver the callbacks recorded so far to each client (mt_events_drain). */
@@ -719,6 +730,64 @@ class BatchClient {
         return undefined;
     }
 
+    // ---- local references (localReference.ts; client.ts:294-300; include/mtgpu.h "local references"):
+    // the (segment, offset) pairs live on the device and follow the document's edits there
+    /** new LocalReference at getContainingSegment(pos) of the local view + addLocalReference */
+    createLocalReference(pos, refType = ReferenceType.Simple) {
+        const ref = new LocalReference(this, undefined, 0, refType);
+        this._addRef(ref, pos);
+        return ref;
+    }
+    /** Client.addLocalReference (client.ts:294-296) of a LocalReference made on a segment descriptor */
+    addLocalReference(lref) {
+        if (lref.handle !== undefined) throw new Error("BatchClient.addLocalReference: the reference is already added");
+        if (!lref._at) throw new Error("BatchClient.addLocalReference: the reference names no segment");
+        if (lref._at.segment.removedSeq !== undefined) {
+            throw new Error("BatchClient.addLocalReference: a reference on a removed segment is not supported");
+        }
+        this._addRef(lref, this.getPosition(lref._at.segment) + lref._at.offset);
+    }
+    _addRef(ref, pos) {
+        this.engine._enableRefs();
+        this.engine.flush();
+        this._checkError();
+        const a = Buffer.alloc(12);
+        a.writeUInt32LE(this.doc, 0);
+        a.writeInt32LE(pos, 4);
+        a.writeUInt32LE(ref.refType & 0xffff, 8);
+        const h = native.refsAdd(this.engine.handle, a).readUInt32LE(0);
+        if (h === REF_NONE) throw new Error(`BatchClient: no segment at position ${pos} for a local reference`);
+        if (h === REF_FULL) throw new Error("BatchClient: the document's local-reference table is full (refsPerDoc)");
+        ref.handle = h;
+        ref._at = undefined;
+    }
+    /** Client.removeLocalReference (client.ts:298-300) */
+    removeLocalReference(lref) {
+        if (lref.handle === undefined) return;
+        this.engine.flush();
+        const d = Buffer.alloc(4), h = Buffer.alloc(4);
+        d.writeUInt32LE(this.doc, 0);
+        h.writeUInt32LE(lref.handle, 0);
+        native.refsRemove(this.engine.handle, d, h);
+        lref.handle = undefined;
+    }
+    /** [{position, ordinal, offset}] of this document's reference handles (one device call) */
+    _refPositions(handles) {
+        this.engine.flush();
+        this._checkError();
+        const d = Buffer.alloc(4 * handles.length), h = Buffer.alloc(4 * handles.length);
+        handles.forEach((x, i) => { d.writeUInt32LE(this.doc, 4 * i); h.writeUInt32LE(x, 4 * i); });
+        const r = native.refsPositions(this.engine.handle, d, h);
+        return handles.map((x, i) => ({ position: r.readInt32LE(12 * i), ordinal: r.readInt32LE(12 * i + 4),
+            offset: r.readUInt32LE(12 * i + 8) }));
+    }
+    _descriptorAt(ordinal) {
+        const r = this._resolve(POS_OF_ORDINAL, ordinal);
+        return r.ordinal >= 0 ? this._descriptor(r.ordinal, r.position, r.length) : undefined;
+    }
+    /** SharedSegmentSequence.localRefToPos (sequence.ts): the reference's position, -1 when detached */
+    referencePositionToLocalPosition(ref) { return ref.toPosition(); }
+
     // ---- TestClient helpers (src/test/testClient.ts:112-234) --------------------------------
     makeOpMessage(op, seq = -1, refSeq = this.currentSeq, longClientId, minSeqNumber = 0) {
         return { clientId: longClientId === undefined ? this.longClientId : longClientId, clientSequenceNumber: 1,
@@ -752,4 +821,4 @@ class BatchClient {
     }
 }
 
-module.exports = { BatchEngine, BatchClient, native };
+module.exports = { BatchEngine, BatchClient, LocalReference, ReferenceType, native };

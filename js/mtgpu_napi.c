@@ -539,6 +539,71 @@ static napi_value events_enable(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* refsEnable(engine, perDoc): room for local references (mt_refs_enable; after eventsEnable) */
+static napi_value refs_enable(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t per = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &per));
+    engine_box* b = get_box(env, argv[0]);
+    if (!b) return throw_status(env, "mt_refs_enable", MT_ERR_ARG);
+    enter(b);
+    mt_status st = mt_refs_enable(b->e, per);
+    leave(b);
+    if (st) return throw_status(env, "mt_refs_enable", st);
+    return NULL;
+}
+
+/* refsAdd(engine, adds (12-byte mt_ref_add rows)) -> Buffer of u32 handles */
+static napi_value refs_add(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], out;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 2 ? get_box(env, argv[0]) : NULL;
+    size_t na = 0;
+    const void* a = b ? buffer_data(env, argv[1], &na) : NULL;
+    if (!b || na % sizeof(mt_ref_add)) {
+        napi_throw_type_error(env, NULL, "refsAdd(engine, adds)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(na / sizeof(mt_ref_add));
+    void* data = NULL;
+    NAPI_CALL(env, napi_create_buffer(env, n ? n * sizeof(uint32_t) : 1, &data, &out));
+    enter(b);
+    mt_status st = mt_refs_add(b->e, (const mt_ref_add*)a, n, (uint32_t*)data);
+    leave(b);
+    if (st) return throw_status(env, "mt_refs_add", st);
+    return out;
+}
+
+/* refsRemove(engine, docs (u32 rows), handles (u32 rows)); refsPositions(engine, docs, handles) ->
+ * Buffer of 12-byte mt_ref_pos rows */
+static napi_value refs_by_handle(napi_env env, napi_callback_info info, int positions) {
+    size_t argc = 3;
+    napi_value argv[3], out = NULL;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 3 ? get_box(env, argv[0]) : NULL;
+    size_t nd = 0, nh = 0;
+    const void* docs = b ? buffer_data(env, argv[1], &nd) : NULL;
+    const void* hs = b ? buffer_data(env, argv[2], &nh) : NULL;
+    if (!b || nd % 4 || nd != nh) {
+        napi_throw_type_error(env, NULL, positions ? "refsPositions(engine, docs, handles)" : "refsRemove(engine, docs, handles)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(nd / 4);
+    void* data = NULL;
+    if (positions) NAPI_CALL(env, napi_create_buffer(env, n ? n * sizeof(mt_ref_pos) : 1, &data, &out));
+    enter(b);
+    mt_status st = positions ? mt_refs_positions(b->e, (const uint32_t*)docs, (const uint32_t*)hs, n, (mt_ref_pos*)data)
+                             : mt_refs_remove(b->e, (const uint32_t*)docs, (const uint32_t*)hs, n);
+    leave(b);
+    if (st) return throw_status(env, positions ? "mt_refs_positions" : "mt_refs_remove", st);
+    return out;
+}
+static napi_value refs_remove(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 0); }
+static napi_value refs_positions(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 1); }
+
 /* eventsDrain(engine, nDocs) -> [Buffer of 64-byte mt_event rows, Buffer of nDocs+1 u32 row pointers] */
 static napi_value events_drain(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -691,6 +756,10 @@ static napi_value init(napi_env env, napi_value exports) {
         {"segmentText", NULL, segment_text, NULL, NULL, NULL, napi_default, NULL},
         {"regenDrain", NULL, regen_drain, NULL, NULL, NULL, napi_default, NULL},
         {"eventsDrain", NULL, events_drain, NULL, NULL, NULL, napi_default, NULL},
+        {"refsEnable", NULL, refs_enable, NULL, NULL, NULL, napi_default, NULL},
+        {"refsAdd", NULL, refs_add, NULL, NULL, NULL, napi_default, NULL},
+        {"refsRemove", NULL, refs_remove, NULL, NULL, NULL, napi_default, NULL},
+        {"refsPositions", NULL, refs_positions, NULL, NULL, NULL, napi_default, NULL},
         {"createDeli", NULL, create_deli, NULL, NULL, NULL, napi_default, NULL},
         {"deliTicket", NULL, deli_ticket, NULL, NULL, NULL, napi_default, NULL},
         {"deliError", NULL, deli_error, NULL, NULL, NULL, napi_default, NULL},
