@@ -4,7 +4,10 @@
 // client.ts:797-828, bit-exact); a different home for the document state:
 //
 //   * every per-segment field the op path touches lives in VGPRs, BLOCKED by lane: slot i of
-//     the document is register j = i % K of lane i / K (K = CAP / 64).  The visibility of every
+//     the document is register j = i % K of lane i / K (K = CAP / 64).  seq and removedSeq share a
+//     register, as 15-bit offsets into the launch's collab window (mt_seqwin.h): the op path only
+//     compares them there, the exact numbers are rebuilt at the store, and a launch that does not
+//     fit the window runs on mt_apply.hip (mt_bin_kernel).  The visibility of every
 //     segment for an op's (refSeq, client) view (mergeTree.ts:1667-1697) is K per-lane
 //     evaluations plus one wave-wide DPP scan: the PartialSequenceLengths query
 //     (partialLengths.ts:433-487) without any memory traffic;
@@ -28,6 +31,7 @@
 #include <stdint.h>
 
 #include "../../include/mtgpu.h"
+#include "mt_seqwin.h"
 #include "mt_state.h"
 #include "mt_wave.h"
 
@@ -41,7 +45,7 @@ constexpr uint32_t kLenBits = 17;      // li = len | id << 17  (len <= textcap <
 constexpr uint32_t kLenMask = (1u << kLenBits) - 1;
 constexpr uint32_t kNoId = 0x7FFFu;    // id of a padding slot
 constexpr uint32_t kEmptyLi = kNoId << kLenBits;
-// cf = client (bits 0-7) | removedClientId (8-15) | segment flags (16-23)
+// cf = client (bits 0-7) | removedClientId (8-15) | segment flags (16-21) | origin (22-31, below)
 constexpr uint32_t F_RM = (uint32_t)MT_SF_REMOVED << 16;
 constexpr uint32_t F_PDEF = (uint32_t)MT_SF_PDEF << 16;
 constexpr uint32_t F_NL = (uint32_t)MT_SF_NL << 16;
@@ -52,6 +56,10 @@ constexpr uint32_t F_MARKER = (uint32_t)MT_SF_MARKER << 16;
 // where it is read -- scour's append decisions (the block's children at once) and the store.
 constexpr uint32_t F_NLQ = 1u << 21;
 constexpr uint32_t kEmptyCf = 0xFFu;     // padding: client 255 never matches (and the slot is dead)
+// cf bits 22-31: the segment's origin, the position at load of the segment it descends from (a
+// boundary split's right part inherits it with seq / rseq).  The row of the exact seq / rseq of a
+// segment whose offset is 0 (mt_seqwin.h); 0 and unread on a segment the launch inserted.
+constexpr uint32_t kOrgShift = 22;
 constexpr uint16_t kDead = 0xFFFFu;
 
 // The document arrays are read and written through global-address-space pointers (global_load /
@@ -158,7 +166,8 @@ struct RLds {
 };
 
 struct Elem {
-    int32_t seq, rseq;
+    uint32_t sw;  // seq | rseq as window offsets (mt_seqwin.h); the exact seq in the classes that keep rsq
+    uint32_t rsq;  // (those classes) the exact rseq
     uint32_t li, cf, ov, oh;
     int32_t cum;
 };
@@ -189,12 +198,20 @@ struct RWave {
 
     // ---- document state in registers (blocked: slot i = lane * K + j).  ext vectors: SSA values
     // end to end, and a wave-uniform dynamic index becomes s_set_gpr_idx register indexing.
-    VI seq, rseq;
+    // sw: seq and rseq as offsets from base_seq, the document's min_seq at load (mt_seqwin.h): the
+    // op path only compares them inside the collab window; store() rebuilds the exact numbers
+    // The classes up to K = MT_SW_EXACT_K (documents of <= 192 slots) have no scratch or occupancy to
+    // win from the fifth register and paid for the packing (C5 -1.3 %): they keep the exact numbers,
+    // seq in sw and rseq in rsq, and run any launch.
+    static constexpr bool PK = K > MT_SW_EXACT_K;
+    VU sw;
+    VU rsq;  // (!PK) rseq
     VU li, cf, ov;
     VU oh;   // (W only) overlap clients 33..63
     VI cum;  // per-op scratch: inclusive visible prefix for the op's view
     // ---- uniform document scalars
     int ns, nlive, nb0, nlev, heap_n, cur_seq, min_seq, err, err_seq, next_id;
+    int32_t base_seq;  // min_seq at load: the origin of the offsets in sw
     uint32_t text_top, text_half;
     bool dirty;  // arena stores issued and not yet waited for
     uint32_t pb; // the current op's payload, prefetched: lane i holds byte i (i < 64)
@@ -225,6 +242,14 @@ struct RWave {
     }
     MT_DEV static uint32_t len_of(uint32_t l) { return l & kLenMask; }
     MT_DEV static uint32_t id_of(uint32_t l) { return l >> kLenBits; }
+    // ---- seq / rseq compares in the class's form.  A reference or minimum sequence number as the
+    // compares' limit, and an op's seq as the key rseq is set to and tested for
+    MT_DEV uint32_t lim_of(int32_t R) const { return PK ? mt_sw_lim(R, base_seq) : (uint32_t)R; }
+    MT_DEV uint32_t key_of(int32_t S) const { return PK ? mt_sw_off(S, base_seq) : (uint32_t)S; }
+    MT_DEV static bool key_le(uint32_t a, uint32_t lim) { return PK ? a <= lim : (int32_t)a <= (int32_t)lim; }
+    MT_DEV bool seq_le(int j, uint32_t lim) const { return PK ? mt_sw_seq_le(sw[j], lim) != 0 : (int32_t)sw[j] <= (int32_t)lim; }
+    MT_DEV bool rseq_le(int j, uint32_t lim) const { return PK ? mt_sw_rseq_le(sw[j], lim) != 0 : (int32_t)rsq[j] <= (int32_t)lim; }
+    MT_DEV bool rseq_eq(int j, uint32_t key) const { return PK ? mt_sw_rseq_eq(sw[j], key) != 0 : rsq[j] == key; }
 
     // ------------------------------------------------------------ slot masks
     MT_DEV uint32_t bs_bits() const { return bsm; }
@@ -361,11 +386,12 @@ struct RWave {
     // it is set, null for a rewrite's null-valued key).  tm: the op's touched slots.
     MT_DEV void emit_range(bool is_remove, int32_t S, int C, uint32_t tm, uint64_t pclr, uint64_t pset, bool rewrite) {
         uint32_t hm = 0;
+        const uint32_t dS = key_of(S);
 #pragma unroll
         for (int j = 0; j < K; j++) {
             const uint32_t f = cf[j];
             const bool hit = ((tm >> j) & 1u) &&
-                             (!is_remove || ((f & F_RM) && rseq[j] == S && ((f >> 8) & 0xFFu) == (uint32_t)C));
+                             (!is_remove || ((f & F_RM) && rseq_eq(j, dS) && ((f >> 8) & 0xFFu) == (uint32_t)C));
             hm |= hit ? (1u << j) : 0u;
         }
         const int hc = __popc(hm);
@@ -423,18 +449,6 @@ struct RWave {
     }
 
     // ------------------------------------------------------------ element access
-    MT_DEV Elem get(int k) const {  // all fields of the slot at uniform position k
-        const int lk = k / K, jk = uni(k % K);
-        Elem r;
-        r.seq = __builtin_amdgcn_readlane(seq[jk], lk);
-        r.rseq = __builtin_amdgcn_readlane(rseq[jk], lk);
-        r.li = (uint32_t)__builtin_amdgcn_readlane((int)li[jk], lk);
-        r.cf = (uint32_t)__builtin_amdgcn_readlane((int)cf[jk], lk);
-        r.ov = (uint32_t)__builtin_amdgcn_readlane((int)ov[jk], lk);
-        if constexpr (W) r.oh = (uint32_t)__builtin_amdgcn_readlane((int)oh[jk], lk);
-        r.cum = __builtin_amdgcn_readlane(cum[jk], lk);
-        return r;
-    }
     MT_DEV uint32_t get_li(int k) const {
         const int jk = uni(k % K);
         return (uint32_t)__builtin_amdgcn_readlane((int)li[jk], k / K);
@@ -458,7 +472,8 @@ struct RWave {
     template <bool CUM>
     MT_DEV void shift_in(int p, const Elem& e, bool bs, int scv, bool live, bool dup = false) {
         mask_shift(p, bs, scv, live);
-        const int32_t c_seq = shr1(seq[K - 1], 0), c_rseq = shr1(rseq[K - 1], 0);
+        const uint32_t c_sq = (uint32_t)shr1((int)sw[K - 1], 0);
+        const uint32_t c_rq = PK ? 0u : (uint32_t)shr1((int)rsq[K - 1], 0);
         const uint32_t c_li = (uint32_t)shr1((int)li[K - 1], 0), c_cf = (uint32_t)shr1((int)cf[K - 1], 0);
         const uint32_t c_ov = (uint32_t)shr1((int)ov[K - 1], 0);
         const uint32_t c_oh = W ? (uint32_t)shr1((int)oh[K - 1], 0) : 0u;
@@ -471,10 +486,13 @@ struct RWave {
 #pragma unroll
         for (int j = K - 1; j >= 0; j--) {
             const bool mv = j > rq, at = j == ra;
-            const int32_t pseq = j ? seq[j - 1] : c_seq, prseq = j ? rseq[j - 1] : c_rseq;
+            const uint32_t psq = j ? sw[j - 1] : c_sq;
             const uint32_t pli = j ? li[j - 1] : c_li, pcf = j ? cf[j - 1] : c_cf, pov = j ? ov[j - 1] : c_ov;
-            seq[j] = mv ? pseq : (at ? e.seq : seq[j]);
-            rseq[j] = mv ? prseq : (at ? e.rseq : rseq[j]);
+            sw[j] = mv ? psq : (at ? e.sw : sw[j]);
+            if constexpr (!PK) {
+                const uint32_t prq = j ? rsq[j - 1] : c_rq;
+                rsq[j] = mv ? prq : (at ? e.rsq : rsq[j]);
+            }
             li[j] = mv ? pli : (at ? e.li : li[j]);
             cf[j] = mv ? pcf : (at ? e.cf : cf[j]);
             ov[j] = mv ? pov : (at ? e.ov : ov[j]);
@@ -508,21 +526,23 @@ struct RWave {
 
     // ------------------------------------------------------------ visibility
     // nodeLength leaf branch for a remote client (mergeTree.ts:1667-1697); dead slots have length 0
-    MT_DEV int vis(int j, int32_t R, int C) const {
+    // (Rw: R as the compares' limit, lim_of)
+    MT_DEV int vis(int j, uint32_t Rw, int C) const {
         // bitwise, not short-circuit: no branch per slot
         const uint32_t f = cf[j];
-        const bool seen = ((f & 0xFFu) == (uint32_t)C) | (seq[j] <= R);
+        const bool seen = ((f & 0xFFu) == (uint32_t)C) | seq_le(j, Rw);
         const uint32_t ovw = (W && C > kNarrowClients) ? oh[j] : ov[j];
         const bool hid = ((f & F_RM) != 0) & ((((f >> 8) & 0xFFu) == (uint32_t)C) | (((ovw >> ((C - 1) & 31)) & 1u) != 0) |
-                                              (rseq[j] <= R));
+                                              rseq_le(j, Rw));
         return (seen & !hid & (((lvm >> j) & 1u) != 0)) ? (int)len_of(li[j]) : 0;
     }
     // cum = inclusive prefix of vis over the slots; returns getLength(R, C)
     MT_DEV int scan(int32_t R, int C) {
         int acc = 0;
+        const uint32_t Rw = lim_of(R);
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            acc += vis(j, R, C);
+            acc += vis(j, Rw, C);
             cum[j] = acc;
         }
         const int incl = wave_incl_scan(acc);
@@ -966,7 +986,7 @@ struct RWave {
         for (int j = 0; j < K; j++) {
             const int q = rbase + __popc(lb & ((1u << j) - 1u));
             uint32_t* const z = ((lb >> j) & 1u) ? &s.zr[q] : dum;
-            z[0] = (uint32_t)((cf[j] & F_RM) ? rseq[j] : seq[j]);
+            z[0] = PK ? ((cf[j] & F_RM) ? mt_sw_drseq(sw[j]) : mt_sw_dseq(sw[j])) : ((cf[j] & F_RM) ? rsq[j] : sw[j]);
             z[kMaxNodes] = li[j];
             z[2 * kMaxNodes] = cf[j];
             z[3 * kMaxNodes] = (uint32_t)idx(j);
@@ -978,7 +998,7 @@ struct RWave {
         const int zq = lane & (kMaxNodes - 1);
         const uint32_t r0 = s.zr[zq], r1 = s.zr[kMaxNodes + zq], r2 = s.zr[2 * kMaxNodes + zq],
                        r3 = s.zr[3 * kMaxNodes + zq];
-        const int32_t vsq = mine ? (int32_t)r0 : 0;
+        const uint32_t vsq = mine ? r0 : 0u;  // (in the class's form: compared by key_le)
         const uint32_t vli = mine ? r1 : 0u;
         uint32_t vcf = mine ? r2 : 0u;
         const int vslot = mine ? (int)r3 : 0;
@@ -997,10 +1017,10 @@ struct RWave {
         // (canAppend textSegment.ts:63-68, matchProperties properties.ts:62-93) -- the run's
         // newline and props are those of child q-1 -- and the run or q is within
         // TextSegmentGranularity; only that last clause depends on earlier decisions
-        const int32_t minSeq = min_seq;
+        const uint32_t minSeq = lim_of(min_seq);
         const bool rm = mine && (vcf & F_RM) != 0;
         const uint32_t ql = len_of(vli);
-        const bool elig = mine && !rm && vsq <= minSeq && ql > 0;
+        const bool elig = mine && !rm && key_le(vsq, minSeq) && ql > 0;
         const bool pelig = shr1(elig ? 1 : 0, 0) != 0;
         const uint32_t pcf = (uint32_t)shr1((int)vcf, 0);
         const uint32_t pprl = (uint32_t)shr1((int)(uint32_t)vpr, 0);
@@ -1026,7 +1046,7 @@ struct RWave {
                 }
             }
         }
-        const uint32_t unlink = (uint32_t)__ballot(rm && vsq <= minSeq) | appm;
+        const uint32_t unlink = (uint32_t)__ballot(rm && key_le(vsq, minSeq)) | appm;
         const int kept = cnt - __popc(unlink);
         // lane q appended: the child of the run's head, the last child before q not appended
         const uint32_t heads = ~appm & ((1u << (lane & 31)) - 1u);
@@ -1269,13 +1289,14 @@ struct RWave {
         // end of the block (:2431-2444)
         int best = 0x7fffffff;
         {
+            const uint32_t Rw = lim_of(R);
             const int cs = cs0();
 #pragma unroll
             for (int j = K - 1; j >= 0; j--) {
                 const int i = idx(j);
                 const int ce = cum[j];
                 const int csj = j ? cum[j - 1] : cs;
-                const bool rm_before = ((cf[j] & F_RM) != 0) & (rseq[j] <= R);
+                const bool rm_before = ((cf[j] & F_RM) != 0) & rseq_le(j, Rw);
                 const bool h = (((lvm >> j) & 1u) != 0) & (i >= a) & (i < e) &
                                ((ce > pos) | ((ce == pos) & (csj == pos) & !rm_before));
                 best = h ? i : best;
@@ -1312,8 +1333,8 @@ struct RWave {
         }
         text_top = top + (uint32_t)tlen;
         wave_sync();
-        en.seq = S;
-        en.rseq = 0;
+        en.sw = PK ? mt_sw_pack(mt_sw_off(S, base_seq), 0u) : (uint32_t)S;
+        en.rsq = 0;
         en.li = (uint32_t)tlen | ((uint32_t)t << kLenBits);
         en.cf = (uint32_t)C | fl;
         en.ov = 0;
@@ -1342,6 +1363,7 @@ struct RWave {
                 pset = (pset & ~m) | ((uint64_t)pbyte(pay, tlen + 2 * q + 1) << (8 * k));
             }
         }
+        const uint32_t dS = key_of(S);
         uint32_t tm = 0;  // touched slots of this lane
         {
             int cs = cs0();
@@ -1365,7 +1387,8 @@ struct RWave {
                 const bool overlap = touched && was_rm;  // addOverlappingClient
                 ov[j] = (overlap && !hic) ? (ov[j] | cbit) : ov[j];
                 if constexpr (W) oh[j] = (overlap && hic) ? (oh[j] | cbit) : oh[j];
-                rseq[j] = mark ? S : rseq[j];
+                if constexpr (PK) sw[j] = mark ? mt_sw_with_drseq(sw[j], dS) : sw[j];
+                else rsq[j] = mark ? dS : rsq[j];
                 cf[j] = mark ? ((f & ~0xFF00u) | F_RM | ((uint32_t)C << 8)) : f;
             }
         } else {
@@ -1437,7 +1460,11 @@ struct RWave {
                   : (np > 0 && kmax >= MT_MAX_KEYS) ? MT_DERR_LIMITS
                   : (op.pos1 < 0 || (!ins && op.pos2 < 0)) ? MT_DERR_BAD_OP
                   : !(cur_seq < S) ? MT_DERR_SEQ_ORDER
-                  : (!(min_seq <= op.msn) || !(op.msn <= S)) ? MT_DERR_MSN_ORDER : 0;
+                  : (!(min_seq <= op.msn) || !(op.msn <= S)) ? MT_DERR_MSN_ORDER
+                  // an op outside the launch's offset window (mt_seqwin.h) would see a wrong view:
+                  // mt_bin_kernel sends such a launch to the LDS engine, so this halt is never taken
+                  // -- and never silent if it is
+                  : (PK && !mt_sw_fits(S, op.ref_seq, base_seq)) ? MT_DERR_LIMITS : 0;
             if (bad) fail(bad, S);
         }
         if (!noop && !bad) {
@@ -1478,8 +1505,8 @@ struct RWave {
                     t = uni(t);
 #ifdef MT_UNI_ELEM
                     // (the inserted element and the cut as scalars: 4-8 B less scratch in most classes)
-                    e.seq = uni(e.seq);
-                    e.rseq = uni(e.rseq);
+                    e.sw = uniu(e.sw);
+                    e.rsq = uniu(e.rsq);
                     e.li = uniu(e.li);
                     e.cf = uniu(e.cf);
                     e.ov = uniu(e.ov);
@@ -1638,13 +1665,15 @@ struct RWave {
     // interior-level rows by chunks of 64) and waited for once, then the LDS images and the register
     // state are built from the registers.  (Before: a loop per array with a dependent load per
     // iteration, ~20 serialized memory round trips per launch.)
-    MT_DEV void load(KGState& g, uint32_t d) {
+    // false: the state does not fit the offset window (the document is halted in HBM; nothing to apply or store)
+    MT_DEV bool load(KGState& g, uint32_t d) {
         const MT_GLOB mt_doc_scalars& sc = gp(g.sc)[d];
         const int n = uni(sc.nseg);
         nlev = uni(sc.nlev);
         heap_n = uni(sc.heap_n);
         cur_seq = uni(sc.cur_seq);
         min_seq = uni(sc.min_seq);
+        base_seq = min_seq;
         err = uni(sc.err);
         err_seq = uni(sc.err_seq);
         text_top = uniu(sc.text_top);
@@ -1757,23 +1786,43 @@ struct RWave {
         }
         wave_sync();
         // ---- 3. the register state (padding past n: dead, length 0, client 255)
+        bool wide_sq = false;  // a number of the state past the offset window (mt_bin_kernel rules it out)
         bsm = lvm = sc0 = sc1 = 0u;
 #pragma unroll
         for (int j = 0; j < K; j++) {
             const bool in = i0 + j < n;
+            const bool rmj = (byte_at(bfw, j) & MT_SF_REMOVED) != 0;
             const int mk = s.scr[i0 + j];  // scr[i] for i >= n is harmless (selected away)
-            seq[j] = in ? (int32_t)vsq[j] : 0x7fffffff;
-            rseq[j] = in ? (int32_t)vrs[j] : 0;
+            const uint32_t ds = mt_sw_off((int32_t)vsq[j], base_seq);
+            const uint32_t dr = rmj ? mt_sw_off((int32_t)vrs[j], base_seq) : 0u;
+            if constexpr (PK) {
+                sw[j] = in ? mt_sw_pack(ds, dr) : mt_sw_pack(MT_SW_PAD, 0u);
+                wide_sq |= in & ((ds > MT_SW_MAX) | (dr > MT_SW_MAX));
+            } else {
+                sw[j] = in ? vsq[j] : 0x7fffffffu;
+                rsq[j] = in ? vrs[j] : 0u;
+            }
             li[j] = in ? (vln[j] | ((uint32_t)(i0 + j) << kLenBits)) : kEmptyLi;
             ov[j] = in ? ((ow[2 * j] >> 1) | (ow[2 * j + 1] << 31)) : 0u;
             if constexpr (W) oh[j] = in ? (ow[2 * j + 1] >> 1) : 0u;
-            cf[j] = in ? (byte_at(bcw, j) | (byte_at(brw, j) << 8) | ((byte_at(bfw, j) & 0x1Fu) << 16)) : kEmptyCf;
+            cf[j] = in ? (byte_at(bcw, j) | (byte_at(brw, j) << 8) | ((byte_at(bfw, j) & 0x1Fu) << 16) |
+                          (PK ? (uint32_t)(i0 + j) << kOrgShift : 0u))
+                       : kEmptyCf;
             cum[j] = 0;
             const uint32_t bit = in ? (1u << j) : 0u;
             lvm |= bit;
             bsm |= (mk & 1) ? bit : 0u;
             sc0 |= (mk & 2) ? bit : 0u;
             sc1 |= (mk & 4) ? bit : 0u;
+        }
+        // (the offsets of such a state are not what it held: the document halts as it is in HBM, with
+        // nothing of it stored back)
+        if (__ballot(wide_sq)) {
+            if (lane == 0) {
+                gp(g.sc)[d].err = MT_DERR_LIMITS;
+                gp(g.sc)[d].err_seq = cur_seq;
+            }
+            return false;
         }
         wave_sync();  // (tln shares scr's words: the marks are read)
 #pragma unroll
@@ -1794,8 +1843,8 @@ struct RWave {
                         const int fl = first_lane(em);
                         em &= em - 1;
                         Elem ph;
-                        ph.seq = 0x7fffffff;
-                        ph.rseq = 0;
+                        ph.sw = PK ? mt_sw_pack(MT_SW_PAD, 0u) : 0x7fffffffu;
+                        ph.rsq = 0;
                         ph.li = kEmptyLi;
                         ph.cf = kEmptyCf;
                         ph.ov = 0;
@@ -1809,6 +1858,7 @@ struct RWave {
                 }
             }
         }
+        return true;
     }
 
     // one register field -> HBM in position order, staged through LDS (scattered LDS writes,
@@ -1864,8 +1914,35 @@ struct RWave {
                     if ((q >> j) & 1u) cf[j] = (cf[j] & ~(F_NL | F_NLQ)) | (ch[j] == '\n' ? F_NL : 0u);
             }
         }
-        store_field(seq, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.seq)[so + i] = (int32_t)v; });
-        store_field(rseq, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.rseq)[so + i] = (int32_t)v; });
+        // the exact seq / rseq (mt_seqwin.h): base_seq + offset, and for an offset of 0 the number the
+        // segment's origin row held at load.  Those rows are read here, all of them before the first
+        // row is written: the same wave reads and writes the document, and the passes below stage
+        // every lane's values through LDS, so each of their global stores follows the wait for these
+        // loads.  A lane reads its document's row 0 where it needs none (no branch); rseq is 0 on a
+        // segment that is not removed, as every writer of the rows leaves it.
+        VU xs, xr;
+        if constexpr (PK) {
+            uint32_t as_[K], ar_[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const bool on = (lb >> j) & 1u;
+                const uint32_t org = cf[j] >> kOrgShift;
+                const bool ns_ = on && mt_sw_dseq(sw[j]) == 0u;
+                const bool nr_ = on && (cf[j] & F_RM) && mt_sw_drseq(sw[j]) == 0u;
+                as_[j] = (uint32_t)gp(g.seq)[so + (ns_ ? org : 0u)];
+                ar_[j] = (uint32_t)gp(g.rseq)[so + (nr_ ? org : 0u)];
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                xs[j] = (uint32_t)mt_sw_exact(mt_sw_dseq(sw[j]), base_seq, (int32_t)as_[j]);
+                xr[j] = (cf[j] & F_RM) ? (uint32_t)mt_sw_exact(mt_sw_drseq(sw[j]), base_seq, (int32_t)ar_[j]) : 0u;
+            }
+        } else {  // the classes that keep the exact numbers: as they are
+            xs = sw;
+            xr = rsq;
+        }
+        store_field(xs, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.seq)[so + i] = (int32_t)v; });
+        store_field(xr, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.rseq)[so + i] = (int32_t)v; });
         store_field(ov, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.ovl)[so + i] = (uint64_t)v << 1; });
         if constexpr (W)  // (after the low half: the same rows, read back and completed)
             store_field(oh, lb, pbase, nn, [&](int i, uint32_t v) { gp(g.ovl)[so + i] |= (uint64_t)v << 33; });
@@ -1987,7 +2064,8 @@ MT_DEV KGState& kernarg_gstate() {
     return *p;
 }
 
-// Waves per SIMD by class.  The register state is 6 K VGPRs per lane and the op path needs ~110
+// Waves per SIMD by class.  The register state is 5 K VGPRs per lane from K = 4 up (6 K before round 7,
+// and still at K = 2 and 3, which keep exact seq / rseq) and the op path needs ~110
 // more (text compaction reads no register state: compact_text).  The kernels are issue-latency
 // bound, so a class takes the highest occupancy whose spill stays small.  Round 3 measured K = 4 at
 // 5 waves, K = 6 and 7 at 4 and K = 10 at 3, each with a few bytes of scratch, faster than one wave
@@ -2009,8 +2087,19 @@ MT_DEV KGState& kernarg_gstate() {
 // -1.1 % (profiles/r06_ab/ab8_*); K = 3 at seven (48 B) +1.8 % on C5, K = 2 at eight +0.9 % (both: +1.1 %),
 // K = 2 / 3 at six / five (spill-free) -3.1 % (profiles/r06_ab/ab11_*); K = 5 at five (68 B) its C4 class
 // 65.0 -> 60.9 ms, K = 4 at six neutral (profiles/r06_ab/ab12_*)
+// Round 7 (seq and rseq in one register of window offsets from K = 4 up, mt_seqwin.h: 5 K VGPRs of state there;
+// profiles/r07_resource_usage_reg.txt, profiles/r07_ab/): K = 4, 6, 9 and 10 are spill-free at their
+// occupancy, K = 5 / 7 / 8 keep 40 / 12 / 32 B, K = 11 24 B, and K = 12 fits three waves per SIMD with 48 B
+// (116 B before): its C3 class 31.3 -> 28.9 ms.  (By registers: RLds<12> is ~14.6 KB, so LDS admits 11
+// waves per CU, 2.75 per SIMD, against 8 per CU at two waves.)  C3 345.8 against 339.2 M ops/s, ranges
+// disjoint; C4 and C5 neutral.  K = 2 / 3 keep exact numbers: packed they lost 1.3 % on C5.  Re-picked and
+// kept: K = 5 at four waves (spill-free) its C4 class 60.1 -> 65.0 ms; K = 8 at three (spill-free) its C3
+// class 43.0 -> 45.5 ms.  Replacing cum by a visibility mask and a lane base (two registers for K) was
+// measured and rejected: its consumers rebuild the prefix slot by slot, and the step ran 1.7 % slower on
+// C3 alone and 1.2 % slower on top of the packing.  Four waves at K = 9 / 10 would spill 196 / 272 B at
+// round 6's code (and RLds<10> caps a CU at 12 waves): not tried.
 constexpr int wpe_default(int K) {
-    return K <= 3 ? 7 : K <= 5 ? 5 : K <= 8 ? 4 : K <= 11 ? 3 : 2;
+    return K <= 3 ? 7 : K <= 5 ? 5 : K <= 8 ? 4 : K <= 12 ? 3 : 2;
 }
 // MT_WPE_OV={w0,w1,...,w16} overrides classes one by one (0 = the default), for A/B builds.
 #ifndef MT_WPE_OV
@@ -2033,8 +2122,9 @@ MT_DEV void reg_apply(uint8_t* text, uint32_t textcap, const mt_op_rec* __restri
     const uint32_t b = op_cnt ? min(r1, a + op_cnt) : r1;
     if (a >= b) return;
     PROF_BEGIN(tl, P_LOAD);
-    wv.load(kernarg_gstate(), d);
+    const bool loaded = wv.load(kernarg_gstate(), d);
     PROF_END(wv.prof, P_LOAD, tl);
+    if (!loaded) return;
     // software pipeline: op i's payload was loaded at the end of op i-1's apply and op i+1's is
     // issued at the end of op i's, so every wait for a prefetch finds it a whole op old (a prefetch
     // issued at the top of the loop was waited for at once: the copy into the current-op register,
@@ -2123,7 +2213,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(wpe(K)))) vo
 // MT_WPE_EV_OV overrides them like MT_WPE_OV.  Round 6 (the unrolled op path): K = 6..8 three waves
 // spill-free, K = 9 / 10 / 11 at three 64 / 72 / 144 B -- C3 with events 231.7 -> 260.8 M ops/s (K <= 10),
 // 258.7 -> 269.9 M (K = 11; K = 12 at three loses its class, 37.5 -> 42.7 ms)
-// (profiles/r06_ab/ab13_side_occupancy/).
+// (profiles/r06_ab/ab13_side_occupancy/).  Round 7: K = 10 at three 28 B; K = 11 at three keeps 68 B, above
+// the ~60 B rule, and stays: at two waves (spill-free) C3 with events 270.5 -> 260.4 M ops/s, its class
+// 55.4 -> 63.9 ms (profiles/r07_ab/final_events_ev11.jsonl).  The C64 form's table did not move a class
+// across an occupancy step (at most 44 B, K = 10 at three): unchanged.
 constexpr int wpe_ev_default(int K) { return K <= 2 ? 4 : K <= 11 ? 3 : 2; }
 #ifndef MT_WPE_EV_OV
 #define MT_WPE_EV_OV {0}

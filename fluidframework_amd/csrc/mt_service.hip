@@ -5,6 +5,7 @@
 
 #include "../../include/mtgpu.h"
 #include "mt_checksum.h"
+#include "mt_seqwin.h"
 #include "mt_state.h"
 #include "mt_wave.h"
 
@@ -252,6 +253,9 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
             // fixup consumed, and a halted document's window is never replayed again)
             bool win = ops && sc.win_op == -1 && sc.err == 0;
             int32_t cur = sc.cur_seq, mn = sc.min_seq;
+            // the register engine's offset window (mt_seqwin.h): the largest sequence number of the
+            // launch (and of the state: cur_seq) and the smallest reference sequence number of its ops
+            int32_t s_hi = sc.cur_seq, r_lo = 0x7fffffff;
             for (uint32_t i = a; ops && i < b; i++) {
                 const mt_op_rec o = ops[i];
                 const uint32_t ty = MT_OP_TYPE(o);
@@ -261,6 +265,8 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 nregen += o.seq == MT_SEQ_REGEN ? 1u : 0u;
                 ob += 32ull + o.payload_len;
                 nrem_hi += (ty == MT_OP_REMOVE && o.client >= MT_MAX_CLIENTS) ? 1u : 0u;
+                s_hi = o.seq > s_hi ? o.seq : s_hi;
+                r_lo = (!MT_OP_IS_NOOP(o) && o.ref_seq < r_lo) ? o.ref_seq : r_lo;
                 if (o.type & MT_OP_WIDE) {
                     const uint32_t np = MT_OP_NPAIRS(o);
                     if (np && (!payload || o.payload_len < 3u * np)) {
@@ -351,10 +357,16 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                     if (xk || xo) atomicAdd(&counts[n_buckets + (c - (n_classes + 1))], 1u);
                 }
             }
-            if (!wdoc && c < first_lds && (needs_lds || c64)) {
+            // a launch outside the offset window of the register engine (a reference sequence number
+            // below the document's min_seq, or sequence numbers more than MT_SW_MAX above it; unknown
+            // without the records): the LDS engine, for this launch only
+            // (the classes up to 64 * MT_SW_EXACT_K slots keep exact numbers and run any launch)
+            // (cls, not c: the wide remap above has left c outside the class table, or at -1)
+            const bool off_win = classes[4 * cls] > 64 * MT_SW_EXACT_K && (!ops || !mt_sw_fits(s_hi, r_lo, sc.min_seq));
+            if (!wdoc && c < first_lds && (needs_lds || c64 || off_win)) {
                 // the LDS engine at a register class's capacity, or the register engine's C64 form
                 const int lds_base = n_classes + 1 + (n_classes > first_wide ? n_classes - first_wide : 0);
-                c = (needs_lds ? lds_base : lds_base + first_lds) + c;
+                c = ((needs_lds || off_win) ? lds_base : lds_base + first_lds) + c;
             }
             if (editing) {
                 // the editing documents' buckets (mt_launch_apply_loc): the 1024-slot form at n_classes,
