@@ -73,6 +73,19 @@ extern "C" hipError_t mt_launch_refs_release(const mt_gstate* g, const uint32_t*
                                              uint32_t n_docs, hipStream_t st);
 extern "C" hipError_t mt_launch_refs_free_docs(const mt_gstate* g, const uint32_t* ids, uint32_t n, uint32_t n_docs,
                                                hipStream_t st);
+extern "C" hipError_t mt_launch_refs_resolve_docs(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
+                                                  hipStream_t st);
+extern "C" hipError_t mt_launch_intervals_overlap(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
+                                                  uint32_t n_docs, const uint32_t* row_ptr, uint32_t* counts,
+                                                  uint32_t* out, hipStream_t st);
+extern "C" hipError_t mt_launch_intervals_claim(const mt_gstate* g, const mt_interval_add* in, const mt_pos_result* at,
+                                                uint32_t n, uint32_t n_docs, uint32_t* handles, hipStream_t st);
+extern "C" hipError_t mt_launch_intervals_release(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
+                                                  uint32_t n_docs, uint32_t* removed, hipStream_t st);
+extern "C" hipError_t mt_launch_intervals_free_docs(const mt_gstate* g, const uint32_t* ids, uint32_t n, uint32_t n_docs,
+                                                    hipStream_t st);
+extern "C" hipError_t mt_launch_intervals_gather(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
+                                                 mt_interval_pos* out, hipStream_t st);
 extern "C" hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
                                                uint32_t n_docs, mt_ref_pos* out, hipStream_t st);
 extern "C" hipError_t mt_launch_fixup(const mt_gstate* g, const mt_op_rec* ops, uint32_t n_docs, hipStream_t st);
@@ -529,8 +542,17 @@ mt_status mt_engine_create(const mt_cfg* cfg, mt_engine** out) {
     return MT_OK;
 }
 
-// the local-reference tables (mt_refs_enable)
+// the interval tables (mt_intervals_enable)
+static void intervals_free(mt_engine* e) {
+    if (e->g.ivs) (void)hipFree(e->g.ivs);
+    if (e->g.ivn) (void)hipFree(e->g.ivn);
+    e->g.ivs = nullptr;
+    e->g.ivn = nullptr;
+    e->g.ivcap = 0;
+}
+// the local-reference tables (mt_refs_enable), and the intervals that rest on them
 static void refs_free(mt_engine* e) {
+    intervals_free(e);
     for (void* p : {(void*)e->g.refs, (void*)e->g.refpos, (void*)e->g.refcur, (void*)e->g.refn, (void*)e->g.refq,
                     (void*)e->g.refdrop})
         if (p) (void)hipFree(p);
@@ -548,6 +570,7 @@ static hipError_t refs_clear(mt_engine* e) {
     if (r == hipSuccess) r = hipMemsetAsync(e->g.refn, 0, D * sizeof(uint32_t), e->stream);
     if (r == hipSuccess) r = hipMemsetAsync(e->g.refq, 0, D * sizeof(uint32_t), e->stream);
     if (r == hipSuccess) r = hipMemsetAsync(e->g.refdrop, 0, D * sizeof(uint32_t), e->stream);
+    if (r == hipSuccess && e->g.ivs) r = mt_launch_intervals_free_docs(&e->g, nullptr, e->cfg.max_docs, e->cfg.max_docs, e->stream);
     return r;
 }
 
@@ -710,6 +733,7 @@ mt_status mt_docs_load(mt_engine* e, uint32_t n, const uint32_t* doc_ids, const 
                            reinterpret_cast<mt_load_seg*>(buf + o_sg), buf + o_tx, reinterpret_cast<int32_t*>(buf + o_mn),
                            reinterpret_cast<int32_t*>(buf + o_cs), e->stream) != hipSuccess ||
             mt_launch_refs_free_docs(&e->g, reinterpret_cast<uint32_t*>(buf + o_ids), n, e->n_docs, e->stream) != hipSuccess ||
+            mt_launch_intervals_free_docs(&e->g, reinterpret_cast<uint32_t*>(buf + o_ids), n, e->n_docs, e->stream) != hipSuccess ||
             hipStreamSynchronize(e->stream) != hipSuccess)
             st = MT_ERR_HIP;
     } while (0);
@@ -1030,6 +1054,170 @@ mt_status mt_refs_positions(mt_engine* e, const uint32_t* docs, const uint32_t* 
     if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
     (void)hipFree(buf);
     return r != hipSuccess ? MT_ERR_HIP : st;
+}
+
+// ---- interval collections (include/mtgpu.h; kernels in mt_intervals.hip) -------------------------
+mt_status mt_intervals_enable(mt_engine* e, uint32_t per_doc) {
+    static_assert(sizeof(mt_interval) == 16 && sizeof(mt_interval_add) == 16 && sizeof(mt_interval_query) == 16 &&
+                      sizeof(mt_interval_pos) == 24,
+                  "interval records");
+    if (!e || (per_doc && (!e->g.refs || 2ull * per_doc > e->g.refcap))) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    intervals_free(e);
+    if (!per_doc) return MT_OK;
+    const size_t D = e->cfg.max_docs;
+    if (hipMalloc(&e->g.ivs, D * per_doc * sizeof(mt_interval)) != hipSuccess ||
+        hipMalloc(&e->g.ivn, D * sizeof(uint32_t)) != hipSuccess) {
+        intervals_free(e);
+        return MT_ERR_NOMEM;
+    }
+    e->g.ivcap = per_doc;
+    HIP_OK(mt_launch_intervals_free_docs(&e->g, nullptr, e->cfg.max_docs, e->cfg.max_docs, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return MT_OK;
+}
+
+mt_status mt_intervals_add(mt_engine* e, const mt_interval_add* in, uint32_t n, uint32_t* handles) {
+    if (!e || !e->g.ivs || (n && (!in || !handles))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (in[i].doc >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    if (n == 0) return MT_OK;
+    e->gen++;
+    std::vector<mt_pos_query> q(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        q[2 * i] = mt_pos_query{in[i].doc, in[i].start, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
+        q[2 * i + 1] = mt_pos_query{in[i].doc, in[i].end, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
+    }
+    void* buf = nullptr;
+    const size_t ab = (size_t)n * sizeof(mt_interval_add), qb = 2 * (size_t)n * sizeof(mt_pos_query),
+                 rb = 2 * (size_t)n * sizeof(mt_pos_result), hb = (size_t)n * sizeof(uint32_t);
+    const size_t o_q = ab, o_r = o_q + qb, o_h = o_r + rb;
+    if (hipMalloc(&buf, o_h + hb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* b8 = static_cast<uint8_t*>(buf);
+    auto* da = reinterpret_cast<mt_interval_add*>(b8);
+    auto* dq = reinterpret_cast<mt_pos_query*>(b8 + o_q);
+    auto* dr = reinterpret_cast<mt_pos_result*>(b8 + o_r);
+    auto* dh = reinterpret_cast<uint32_t*>(b8 + o_h);
+    hipError_t r = hipMemcpyAsync(da, in, ab, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(dq, q.data(), qb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_resolve(&e->g, dq, 2 * n, e->n_docs, dr, e->stream);
+    if (r == hipSuccess) r = mt_launch_intervals_claim(&e->g, da, dr, n, e->n_docs, dh, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(handles, dh, hb, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+}
+
+mt_status mt_intervals_remove(mt_engine* e, const mt_interval_query* q, uint32_t n, uint32_t* removed) {
+    if (!e || !e->g.ivs || (n && (!q || !removed))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    if (n == 0) return MT_OK;
+    uint8_t* buf = nullptr;
+    const size_t qb = (size_t)n * sizeof(mt_interval_query), hb = (size_t)n * sizeof(uint32_t);
+    if (hipMalloc(&buf, qb + hb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dq = reinterpret_cast<mt_interval_query*>(buf);
+    auto* dh = reinterpret_cast<uint32_t*>(buf + qb);
+    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_intervals_release(&e->g, dq, n, e->n_docs, dh, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(removed, dh, hb, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+}
+
+mt_status mt_intervals_overlapping_device(mt_engine* e, const mt_interval_query* d_q, uint32_t n,
+                                          const uint32_t* d_row_ptr, uint32_t* d_counts, uint32_t* d_out) {
+    if (!e || !e->g.ivs || (n && (!d_q || !d_counts || (d_row_ptr && !d_out)))) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    HIP_OK(mt_launch_intervals_overlap(&e->g, d_q, n, e->n_docs, d_row_ptr, d_counts, d_out, e->stream));
+    return MT_OK;
+}
+
+mt_status mt_intervals_overlapping(mt_engine* e, const mt_interval_query* q, uint32_t n, uint32_t* row_ptr,
+                                   uint32_t* out, uint64_t cap, uint64_t* total) {
+    if (!e || !e->g.ivs || !row_ptr || !total || (n && !q)) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    row_ptr[0] = 0;
+    *total = 0;
+    if (n == 0) return mt_intervals_overlapping_device(e, nullptr, 0, nullptr, nullptr, nullptr);
+    // the count pass, the rows' prefix sums on the host, then the write pass
+    uint8_t* buf = nullptr;
+    const size_t qb = (size_t)n * sizeof(mt_interval_query), cb = ((size_t)n + 1) * sizeof(uint32_t);
+    if (hipMalloc(&buf, qb + 2 * cb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dq = reinterpret_cast<mt_interval_query*>(buf);
+    auto* dc = reinterpret_cast<uint32_t*>(buf + qb);
+    auto* drp = reinterpret_cast<uint32_t*>(buf + qb + cb);
+    uint32_t* dout = nullptr;
+    mt_status st = MT_OK;
+    do {
+        std::vector<uint32_t> cnt(n);
+        if (hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            (st = mt_intervals_overlapping_device(e, dq, n, nullptr, dc, nullptr)) != MT_OK ||
+            hipMemcpyAsync(cnt.data(), dc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            if (st == MT_OK) st = MT_ERR_HIP;
+            break;
+        }
+        uint64_t sum = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            sum += cnt[i];
+            if (sum >= (1ull << 32)) break;
+            row_ptr[i + 1] = (uint32_t)sum;
+        }
+        if (sum >= (1ull << 32)) {
+            st = MT_ERR_ARG;
+            break;
+        }
+        *total = sum;
+        if (!out || sum == 0) break;
+        if (cap < sum) {
+            st = MT_ERR_ARG;
+            break;
+        }
+        if (hipMalloc(&dout, sum * sizeof(uint32_t)) != hipSuccess) {
+            st = MT_ERR_NOMEM;
+            break;
+        }
+        if (hipMemcpyAsync(drp, row_ptr, cb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            (st = mt_intervals_overlapping_device(e, dq, n, drp, dc, dout)) != MT_OK ||
+            hipMemcpyAsync(out, dout, sum * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            if (st == MT_OK) st = MT_ERR_HIP;
+        }
+    } while (0);
+    if (dout) (void)hipFree(dout);
+    (void)hipFree(buf);
+    return st;
+}
+
+mt_status mt_intervals_positions(mt_engine* e, const uint32_t* docs, uint32_t n, mt_interval_pos* out) {
+    if (!e || !e->g.ivs || (n && (!docs || !out))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
+    if (n == 0) return MT_OK;
+    uint8_t* buf = nullptr;
+    const size_t db = ((size_t)n * sizeof(uint32_t) + 15) & ~size_t(15), ob = (size_t)n * e->g.ivcap * sizeof(mt_interval_pos);
+    if (hipMalloc(&buf, db + ob) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dd = reinterpret_cast<uint32_t*>(buf);
+    auto* dout = reinterpret_cast<mt_interval_pos*>(buf + db);
+    hipError_t r = hipMemcpyAsync(dd, docs, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_refs_resolve_docs(&e->g, dd, n, e->n_docs, e->stream);
+    if (r == hipSuccess) r = mt_launch_intervals_gather(&e->g, dd, n, e->n_docs, dout, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
 }
 
 mt_status mt_batch_upload(mt_engine* e, const mt_op_rec* ops, uint64_t n_ops, const uint8_t* payload,

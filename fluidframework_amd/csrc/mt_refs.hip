@@ -149,8 +149,8 @@ struct Tab {
         for (int i = lane; i < T; i += 64) {
             if (t[i].flags == 0u || t[i].ord != L) continue;
             if (t[i].flags & MT_RF_LIVE) {
-                t[i].ord = -1;
-                t[i].off = 0;
+                t[i].ord = -1;  // (off stays: a detached reference keeps its raw offset, which
+                                // LocalReference.compare still reads -- mt_intervals.hip)
             } else {
                 t[i] = mt_ref{-1, 0u, 0u, 0u};
             }
@@ -175,8 +175,7 @@ struct Tab {
                 } else if (tgt < 0 && (t[i].flags & MT_RF_AFTER)) {
                     t[i].flags |= MT_RF_LOOSE;  // clear() skips the `after` lists
                 } else {
-                    t[i].ord = -1;
-                    t[i].off = 0;
+                    t[i].ord = -1;  // lref.segment = undefined: the offset stays (localReference.ts:193, 318)
                 }
             }
         }
@@ -413,6 +412,16 @@ __global__ void mt_refs_gather_kernel(mt_gstate g, const uint32_t* __restrict__ 
     mt_ref_pos r{-1, MT_REF_BAD_HANDLE, 0u};
     if (d < n_docs && h < g.refcap) r = g.refpos[(size_t)d * g.refcap + h];
     out[w] = r;
+}
+
+// steps 1 and 2 alone: g.refpos of documents docs[0..n) answers for every reference they hold
+// (mt_intervals_positions gathers from it)
+extern "C" hipError_t mt_launch_refs_resolve_docs(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
+                                                  hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mt_refs_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *g, docs, n, n_docs);
+    hipLaunchKernelGGL(mt_refs_resolve_kernel, dim3(n_docs), dim3(64), 0, st, *g, n_docs);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,

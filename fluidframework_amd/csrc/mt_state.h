@@ -133,6 +133,16 @@ struct mt_ref {              // 16 bytes
 #define MT_REFQ_ASKED 1u         // mt_gstate.refq bits: queried by the mt_refs_positions call in flight;
 #define MT_REFQ_DIRTY 2u         // pending or zombie entries to settle
 
+// One entry of a document's interval table (mt_intervals.hip; a handle is its index): a
+// SequenceInterval (intervalCollection.ts:107-190) as the handles of its two local references in the
+// document's reference table.  An endpoint detached from birth is a reference entry like any other
+// (ord -1, off 0).
+struct mt_interval {         // 16 bytes
+    uint32_t start, end;     // handles in the document's mt_ref table
+    uint32_t type;           // IntervalType (ops.ts:17-22: Nest 0x1, SlideOnRemove 0x2); bits 16..31: its collection's id
+    uint32_t live;           // 0: a free entry
+};
+
 // Device pointers + capacities (one allocation per array, [n_docs][capacity]).
 struct mt_gstate {
     int32_t* seq;      // [doc][segcap]
@@ -202,5 +212,8 @@ struct mt_gstate {
     uint32_t* refn;    // [doc] entries in use (references and ghosts)
     uint32_t* refq;    // [doc] MT_REFQ_*
     uint32_t* refdrop; // [doc] ghosts dropped for want of room (mt_refs_dropped)
-    uint32_t segcap, lbcap, ibcap, hcap, textcap, evcap, refcap;
+    // interval collections (mt_intervals_enable; null when off)
+    mt_interval* ivs;  // [doc][ivcap]
+    uint32_t* ivn;     // [doc] live intervals
+    uint32_t segcap, lbcap, ibcap, hcap, textcap, evcap, refcap, ivcap;
 };

@@ -113,6 +113,13 @@ def lib():
                          ('mt_refs_positions_device', [vp, vp, vp, u32, vp]), ('mt_refs_dropped', [vp, vp, u32])):
             getattr(L, name).argtypes = at
             getattr(L, name).restype = ctypes.c_int
+        for name, at in (('mt_intervals_enable', [vp, u32]), ('mt_intervals_add', [vp, vp, u32, vp]),
+                         ('mt_intervals_remove', [vp, vp, u32, vp]),
+                         ('mt_intervals_overlapping', [vp, vp, u32, vp, vp, u64, ctypes.POINTER(u64)]),
+                         ('mt_intervals_overlapping_device', [vp, vp, u32, vp, vp, vp]),
+                         ('mt_intervals_positions', [vp, vp, u32, vp])):
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ctypes.c_int
         L.mt_version.restype = ctypes.c_char_p
         for name in ('mt_engine_create', 'mt_engine_destroy', 'mt_docs_init', 'mt_batch_upload', 'mt_batch_apply',
                      'mt_batch_free', 'mt_submit', 'mt_sync', 'mt_get_length', 'mt_get_text', 'mt_get_state',
@@ -418,6 +425,72 @@ class MergeEngine:
         """mt_refs_positions_device: device pointers (ints); complete after the sync done here."""
         _check(lib().mt_refs_positions_device(self.h, d_docs, d_handles, n, d_out), 'mt_refs_positions_device')
         _check(lib().mt_sync(self.h), 'mt_sync')
+
+    # -- interval collections (intervalCollection.ts; include/mtgpu.h) ----------------------------
+    def enable_intervals(self, per_doc=32):
+        """Room for `per_doc` intervals per document (0 frees them).  Needs enable_refs() with room
+        for 2 * per_doc references: an interval is two local references."""
+        _check(lib().mt_intervals_enable(self.h, per_doc), 'mt_intervals_enable')
+        self._iv_per_doc = per_doc
+        return self
+
+    def add_intervals(self, docs, starts, ends, interval_types, collections=0):
+        """addInterval(start, end, intervalType) per entry: one handle each (the lowest free entry of
+        the document's table), refs.REF_FULL where the interval or the reference table is full.
+        `collections`: the id (< 65536) of the document's collection -- its label -- each interval joins;
+        queries and removes see one collection."""
+        from .intervals import INTERVAL_ADD_DTYPE
+        a = np.zeros(len(docs), dtype=INTERVAL_ADD_DTYPE)
+        a['doc'], a['start'], a['end'], a['interval_type'] = docs, starts, ends, interval_types
+        a['collection'] = collections
+        out = np.zeros(len(a), dtype=np.uint32)
+        _check(lib().mt_intervals_add(self.h, _ptr(a), len(a), _ptr(out)), 'mt_intervals_add')
+        return out
+
+    def _interval_queries(self, docs, starts, ends, collections=0):
+        from .intervals import INTERVAL_QUERY_DTYPE
+        q = np.zeros(len(docs), dtype=INTERVAL_QUERY_DTYPE)
+        q['doc'], q['start'], q['end'], q['collection'] = docs, starts, ends, collections
+        return q
+
+    def remove_intervals(self, docs, starts, ends, collections=0):
+        """removeInterval(start, end) per entry: the handle removed, or refs.REF_NONE where no live
+        interval's ends equal the two positions' (segment, offset).  The interval's two references
+        stay in the reference table."""
+        q = self._interval_queries(docs, starts, ends, collections)
+        out = np.zeros(len(q), dtype=np.uint32)
+        _check(lib().mt_intervals_remove(self.h, _ptr(q), len(q), _ptr(out)), 'mt_intervals_remove')
+        return out
+
+    def overlapping_intervals(self, docs, starts, ends, collections=0):
+        """findOverlappingIntervals(start, end) per entry: (handles, row_ptr), query i's handles,
+        ascending, being handles[row_ptr[i]:row_ptr[i + 1]]."""
+        q = self._interval_queries(docs, starts, ends, collections)
+        row_ptr = np.zeros(len(q) + 1, dtype=np.uint32)
+        total = ctypes.c_uint64(0)
+        _check(lib().mt_intervals_overlapping(self.h, _ptr(q), len(q), _ptr(row_ptr), None, 0, ctypes.byref(total)),
+               'mt_intervals_overlapping')  # (the counts alone: how much room the handles take)
+        out = np.zeros(total.value, dtype=np.uint32)
+        if total.value:
+            _check(lib().mt_intervals_overlapping(self.h, _ptr(q), len(q), _ptr(row_ptr), _ptr(out), len(out),
+                                                  ctypes.byref(total)), 'mt_intervals_overlapping')
+        return out, row_ptr
+
+    def overlapping_intervals_device(self, d_queries, n, d_row_ptr, d_counts, d_out):
+        """mt_intervals_overlapping_device: device pointers (ints; d_row_ptr 0 for the count pass);
+        complete after the sync done here."""
+        _check(lib().mt_intervals_overlapping_device(self.h, d_queries, n, d_row_ptr or None, d_counts, d_out or None),
+               'mt_intervals_overlapping_device')
+        _check(lib().mt_sync(self.h), 'mt_sync')
+
+    def interval_positions(self, docs):
+        """intervals.INTERVAL_POS_DTYPE rows [len(docs)][per_doc], indexed by handle: both ends'
+        toPosition() (-1 detached), the intervalType, and live (0: no such interval)."""
+        from .intervals import INTERVAL_POS_DTYPE
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        out = np.zeros((len(d), self._iv_per_doc), dtype=INTERVAL_POS_DTYPE)
+        _check(lib().mt_intervals_positions(self.h, _ptr(d), len(d), _ptr(out)), 'mt_intervals_positions')
+        return out
 
     # -- readout -------------------------------------------------------------------------
     def checksums(self):

@@ -585,6 +585,95 @@ mt_status mt_refs_dropped(mt_engine* eng, uint32_t* out, uint32_t n_docs);
  * document of the engine; the documents not involved leave at once.  Launching over a compacted
  * list of the documents with references / queried is a follow-up. */
 
+/* ---- interval collections ------------------------------------------------------
+ * SharedString.getIntervalCollection(label): packages/dds/sequence/src/intervalCollection.ts:107-243
+ * (SequenceInterval, createPositionReference, createSequenceInterval) and :264-366
+ * (LocalIntervalCollection), over LocalReference.compare (localReference.ts:49-61) and IntervalTree
+ * (collections.ts:1027-1108).  A document keeps up to `per_doc` intervals on the device, each the
+ * handles of two local references in the document's reference table (above) plus its intervalType.
+ *   add     add(start, end, intervalType) makes two references at getContainingSegment(pos) of the local
+ *           view, of type RangeBegin / RangeEnd -- NestBegin / NestEnd when intervalType is exactly
+ *           Nest -- with SlideOnRemove when intervalType has it.  A position with no containing
+ *           segment (below 0, at or past the length) gives an endpoint detached from birth: no segment,
+ *           offset 0; the interval is still made.
+ *   compare everything is decided on (segment, raw `offset`), not on positions, and on `offset`, not
+ *           getOffset(): the offset still counts on a tombstone, and a reference detached by a remove
+ *           keeps it.  a.compare(b): the same segment, or both without one: a.offset - b.offset; a
+ *           without one: -1; b without one: +1; else the order of the two segments among the leaves.
+ *           x.overlaps(q) = x.start.compare(q.end) < 0 && x.end.compare(q.start) >= 0.
+ *   query   findOverlappingIntervals(s, e) builds a transient interval at getContainingSegment(s) /
+ *           (e) and gathers the intervals that overlap it.
+ *   remove  removeInterval(s, e) removes the interval that compares equal to that transient interval,
+ *           endpoint by endpoint.  It never calls removeLocalReference: the interval's two references
+ *           stay live in the reference table -- they keep occupying two reference slots, and keep
+ *           counting for refsByOffset.length on APPEND -- until mt_refs_remove, mt_docs_init or
+ *           mt_docs_load frees them.
+ * The stale tree.  The reference files intervals in a red-black tree whose order and min/max
+ * augmentation are fixed when a node is put, while the references go on moving (they slide; others are
+ * detached and then compare below everything).  Its lookups therefore miss intervals: on the committed
+ * fixture (tests/golden/intervals.expected.jsonl, header row) the tree's answer is a subset of, and on
+ * the logs whose intervals move often smaller than, the intervals x with x.overlaps(q).  The engine
+ * answers the per-interval predicate -- the reference's own overlaps / compare on its own references
+ * at their current place -- and does not reproduce the shape of a stale tree; the fixture records both.
+ * Two differences are kept:
+ *   - where a slide left refsByOffset[offset] without an `at` list the reference's addInterval throws
+ *     in addLocalRef (localReference.ts:212-219), part-way through, with the start reference already
+ *     in; mt_intervals_add makes the interval;
+ *   - a reference whose segment zamboni unlinked keeps that segment in the reference and compares by
+ *     its stale ordinal string; here it is detached (no segment, its raw offset kept).  Two ends on
+ *     the same unlinked segment still compare by offset in both.
+ * Every call folds the documents' events into their references first, as the reference calls do;
+ * nothing runs inside an apply. */
+#define MT_INTERVAL_NEST 0x1u             /* IntervalType.Nest (ops.ts:19) */
+#define MT_INTERVAL_SLIDE_ON_REMOVE 0x2u  /* IntervalType.SlideOnRemove (ops.ts:20) */
+/* A document's collections (one per label) share its table: an interval carries its collection's id,
+ * chosen by the host, and a query or a remove sees the intervals of its own collection only. */
+typedef struct mt_interval_add {   /* 16 bytes */
+    uint32_t doc;
+    int32_t start, end;
+    uint16_t interval_type;
+    uint16_t collection;
+} mt_interval_add;
+typedef struct mt_interval_query { /* 16 bytes */
+    uint32_t doc;
+    int32_t start, end;
+    uint32_t collection;           /* < 65536 */
+} mt_interval_query;
+typedef struct mt_interval_pos {   /* 24 bytes */
+    int32_t start, end;            /* toPosition() of the two ends, -1 detached */
+    uint16_t interval_type;
+    uint16_t collection;
+    uint32_t live;                 /* 0: no interval has this handle (start = end = -1) */
+    uint32_t start_ref, end_ref;   /* the two ends' handles in the reference table (mt_refs_positions) */
+} mt_interval_pos;
+#define MT_INTERVALS_MAX (MT_REFS_MAX / 2u)
+/* Allocate (0 < per_doc <= MT_INTERVALS_MAX) or free (0) the interval tables.  MT_ERR_ARG unless
+ * mt_refs_enable is on with room for 2 * per_doc references.  mt_refs_enable and mt_events_enable free
+ * the tables; mt_docs_init and mt_docs_load free the documents' intervals with their references. */
+mt_status mt_intervals_enable(mt_engine* eng, uint32_t per_doc);
+/* addInterval for a batch: handles[i] names in[i]'s interval within its document (the lowest free
+ * entry), or is MT_REF_FULL when the interval table or the reference table is full -- nothing of the
+ * interval stays behind then, and the document goes on. */
+mt_status mt_intervals_add(mt_engine* eng, const mt_interval_add* in, uint32_t n, uint32_t* handles);
+/* removeInterval for a batch: removed[i] is the handle freed, or MT_REF_NONE where no live interval's
+ * ends equal the two positions' (segment, offset).  Of several equal ones the lowest handle goes. */
+mt_status mt_intervals_remove(mt_engine* eng, const mt_interval_query* q, uint32_t n, uint32_t* removed);
+/* findOverlappingIntervals for a batch, one wave per query: query i's handles, ascending, are
+ * out[row_ptr[i] .. row_ptr[i+1]) (row_ptr: n + 1 entries).  With out == NULL (or cap below the
+ * total: MT_ERR_ARG) only row_ptr / *total are filled.  A document without intervals answers empty. */
+mt_status mt_intervals_overlapping(mt_engine* eng, const mt_interval_query* q, uint32_t n, uint32_t* row_ptr,
+                                   uint32_t* out, uint64_t cap, uint64_t* total);
+/* the same with device-resident arguments (asynchronous on the engine's stream).  d_row_ptr == NULL:
+ * the count pass, d_counts[i] = query i's matches.  Else the write pass: query i's handles go to
+ * d_out[d_row_ptr[i] ..), at most d_row_ptr[i+1] - d_row_ptr[i] of them, and d_counts[i] is still the
+ * whole count -- rows from a count pass's prefix sums, or rows of a capacity the caller chose.  A
+ * query with doc >= n_docs answers empty. */
+mt_status mt_intervals_overlapping_device(mt_engine* eng, const mt_interval_query* d_q, uint32_t n,
+                                          const uint32_t* d_row_ptr, uint32_t* d_counts, uint32_t* d_out);
+/* serialize(): both ends' toPosition() and the intervalType of every entry of documents docs[0..n):
+ * out[i * per_doc + handle], n * per_doc records. */
+mt_status mt_intervals_positions(mt_engine* eng, const uint32_t* docs, uint32_t n, mt_interval_pos* out);
+
 /* ---- bench tooling (not part of the applyMsg boundary) -------------------------------------
  * Synthetic multi-client op streams (DESIGN.md "Synthetic workloads", after SURVEY.md §8d),
  * generated ON THE DEVICE straight into HBM: every document's observer state drives the

@@ -29,6 +29,7 @@ const path = require("path");
 
 const native = require(path.join(__dirname, "mtgpu.node"));
 const { LocalReference, ReferenceType, REF_NONE, REF_FULL } = require(path.join(__dirname, "localReference.js"));
+const { IntervalCollection, IntervalType } = require(path.join(__dirname, "intervalCollection.js"));
 
 const INSERT = 0, REMOVE = 1, ANNOTATE = 2, GROUP = 3, NOOP = 3;
 const F_REWRITE = 1, F_PROPS = 2, F_GROUP_MORE = 4, F_MARKER = 128;
@@ -62,7 +63,11 @@ class BatchEngine {
         this.recording = false;
         this.eventsPerDoc = opts.eventsPerDoc || (1 << 16);
         this.refsOn = false;
-        this.refsPerDoc = opts.refsPerDoc || 64;  // local references per document (mt_refs_enable)
+        this.intervalsOn = false;
+        this.intervalsPerDoc = opts.intervalsPerDoc || 32;  // intervals per document (mt_intervals_enable)
+        // local references per document (mt_refs_enable); every interval takes two of them
+        this.refsPerDoc = opts.refsPerDoc || 64;
+        this.native = native;
         this.labelDecl = [];  // [doc, tile key, range key] to declare before the next submit
         this.gen = 0;         // bumped by every submit: segment descriptors are valid within one generation
         this.syncCallbacks = !!opts.syncCallbacks;  // deliver callbacks before the firing call returns
@@ -82,6 +87,14 @@ class BatchEngine {
         this._enableEvents();
         native.refsEnable(this.handle, this.refsPerDoc);
         this.refsOn = true;
+    }
+
+    /** Interval collections rest on the local references (mt_intervals_enable needs mt_refs_enable). */
+    _enableIntervals() {
+        if (this.intervalsOn) return;
+        this._enableRefs();
+        native.intervalsEnable(this.handle, this.intervalsPerDoc);
+        this.intervalsOn = true;
     }
 
     /** Deliver the callbacks recorded so far to each client (mt_events_drain). */
@@ -788,6 +801,32 @@ class BatchClient {
     /** SharedSegmentSequence.localRefToPos (sequence.ts): the reference's position, -1 when detached */
     referencePositionToLocalPosition(ref) { return ref.toPosition(); }
 
+    // ---- interval collections (sequence/src/intervalCollection.ts; include/mtgpu.h "interval collections")
+    /** SharedSegmentSequence.getIntervalCollection(label) (sequence.ts): the label's collection, made on
+     * first use; `emitter` (optional) receives the local "add" / "delete" value-type ops */
+    getIntervalCollection(label, emitter) {
+        if (!this._intervalCollections) this._intervalCollections = new Map();
+        let c = this._intervalCollections.get(label);
+        if (!c) {
+            c = new IntervalCollection(this, label, this._intervalCollections.size, emitter);
+            this._intervalCollections.set(label, c);
+        }
+        return c;
+    }
+    /** [[{start, end} by handle], [{startRef, endRef} by handle]] of this document's interval table */
+    _intervalPositions() {
+        const d = Buffer.alloc(4);
+        d.writeUInt32LE(this.doc, 0);
+        const per = this.engine.intervalsPerDoc;
+        const r = native.intervalsPositions(this.engine.handle, d, per);
+        const pos = [], refs = [];
+        for (let h = 0; h < per; h++) {
+            pos.push({ start: r.readInt32LE(24 * h), end: r.readInt32LE(24 * h + 4), live: r.readUInt32LE(24 * h + 12) });
+            refs.push({ startRef: r.readUInt32LE(24 * h + 16), endRef: r.readUInt32LE(24 * h + 20) });
+        }
+        return [pos, refs];
+    }
+
     // ---- TestClient helpers (src/test/testClient.ts:112-234) --------------------------------
     makeOpMessage(op, seq = -1, refSeq = this.currentSeq, longClientId, minSeqNumber = 0) {
         return { clientId: longClientId === undefined ? this.longClientId : longClientId, clientSequenceNumber: 1,
@@ -821,4 +860,4 @@ class BatchClient {
     }
 }
 
-module.exports = { BatchEngine, BatchClient, LocalReference, ReferenceType, native };
+module.exports = { BatchEngine, BatchClient, LocalReference, ReferenceType, IntervalCollection, IntervalType, native };

@@ -604,6 +604,106 @@ static napi_value refs_by_handle(napi_env env, napi_callback_info info, int posi
 static napi_value refs_remove(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 0); }
 static napi_value refs_positions(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 1); }
 
+/* intervalsEnable(engine, perDoc): room for intervals (mt_intervals_enable; after refsEnable) */
+static napi_value intervals_enable(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t per = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &per));
+    engine_box* b = get_box(env, argv[0]);
+    if (!b) return throw_status(env, "mt_intervals_enable", MT_ERR_ARG);
+    enter(b);
+    mt_status st = mt_intervals_enable(b->e, per);
+    leave(b);
+    if (st) return throw_status(env, "mt_intervals_enable", st);
+    return NULL;
+}
+
+/* intervalsAdd(engine, adds (16-byte mt_interval_add rows)) -> Buffer of u32 handles;
+ * intervalsRemove(engine, queries (16-byte mt_interval_query rows)) -> Buffer of u32 handles removed */
+static napi_value intervals_by_rows(napi_env env, napi_callback_info info, int add) {
+    size_t argc = 2;
+    napi_value argv[2], out;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 2 ? get_box(env, argv[0]) : NULL;
+    size_t na = 0;
+    const void* a = b ? buffer_data(env, argv[1], &na) : NULL;
+    if (!b || na % 16) {
+        napi_throw_type_error(env, NULL, add ? "intervalsAdd(engine, adds)" : "intervalsRemove(engine, queries)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(na / 16);
+    void* data = NULL;
+    NAPI_CALL(env, napi_create_buffer(env, n ? n * sizeof(uint32_t) : 1, &data, &out));
+    enter(b);
+    mt_status st = add ? mt_intervals_add(b->e, (const mt_interval_add*)a, n, (uint32_t*)data)
+                       : mt_intervals_remove(b->e, (const mt_interval_query*)a, n, (uint32_t*)data);
+    leave(b);
+    if (st) return throw_status(env, add ? "mt_intervals_add" : "mt_intervals_remove", st);
+    return out;
+}
+static napi_value intervals_add(napi_env env, napi_callback_info info) { return intervals_by_rows(env, info, 1); }
+static napi_value intervals_remove(napi_env env, napi_callback_info info) { return intervals_by_rows(env, info, 0); }
+
+/* intervalsOverlapping(engine, queries (16-byte mt_interval_query rows)) ->
+ * [Buffer of u32 handles, Buffer of n + 1 u32 row pointers] */
+static napi_value intervals_overlapping(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], out, hs, rp;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 2 ? get_box(env, argv[0]) : NULL;
+    size_t nq = 0;
+    const void* q = b ? buffer_data(env, argv[1], &nq) : NULL;
+    if (!b || nq % sizeof(mt_interval_query)) {
+        napi_throw_type_error(env, NULL, "intervalsOverlapping(engine, queries)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(nq / sizeof(mt_interval_query));
+    void *rows = NULL, *data = NULL;
+    uint64_t total = 0;
+    NAPI_CALL(env, napi_create_buffer(env, ((size_t)n + 1) * sizeof(uint32_t), &rows, &rp));
+    enter(b);
+    mt_status st = mt_intervals_overlapping(b->e, (const mt_interval_query*)q, n, (uint32_t*)rows, NULL, 0, &total);
+    leave(b);
+    if (st) return throw_status(env, "mt_intervals_overlapping", st);
+    NAPI_CALL(env, napi_create_buffer(env, total ? total * sizeof(uint32_t) : 1, &data, &hs));
+    if (total) {
+        enter(b);
+        st = mt_intervals_overlapping(b->e, (const mt_interval_query*)q, n, (uint32_t*)rows, (uint32_t*)data, total, &total);
+        leave(b);
+        if (st) return throw_status(env, "mt_intervals_overlapping", st);
+    }
+    NAPI_CALL(env, napi_create_array_with_length(env, 2, &out));
+    NAPI_CALL(env, napi_set_element(env, out, 0, hs));
+    NAPI_CALL(env, napi_set_element(env, out, 1, rp));
+    return out;
+}
+
+/* intervalsPositions(engine, docs (u32 rows), perDoc) -> Buffer of docs x perDoc 24-byte mt_interval_pos rows */
+static napi_value intervals_positions(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3], out;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 3 ? get_box(env, argv[0]) : NULL;
+    size_t nd = 0;
+    const void* docs = b ? buffer_data(env, argv[1], &nd) : NULL;
+    uint32_t per = 0;
+    if (b) NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &per));
+    if (!b || nd % 4) {
+        napi_throw_type_error(env, NULL, "intervalsPositions(engine, docs, perDoc)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(nd / 4);
+    void* data = NULL;
+    NAPI_CALL(env, napi_create_buffer(env, (size_t)n * per ? (size_t)n * per * sizeof(mt_interval_pos) : 1, &data, &out));
+    enter(b);
+    mt_status st = mt_intervals_positions(b->e, (const uint32_t*)docs, n, (mt_interval_pos*)data);
+    leave(b);
+    if (st) return throw_status(env, "mt_intervals_positions", st);
+    return out;
+}
+
 /* eventsDrain(engine, nDocs) -> [Buffer of 64-byte mt_event rows, Buffer of nDocs+1 u32 row pointers] */
 static napi_value events_drain(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -760,6 +860,11 @@ static napi_value init(napi_env env, napi_value exports) {
         {"refsAdd", NULL, refs_add, NULL, NULL, NULL, napi_default, NULL},
         {"refsRemove", NULL, refs_remove, NULL, NULL, NULL, napi_default, NULL},
         {"refsPositions", NULL, refs_positions, NULL, NULL, NULL, napi_default, NULL},
+        {"intervalsEnable", NULL, intervals_enable, NULL, NULL, NULL, napi_default, NULL},
+        {"intervalsAdd", NULL, intervals_add, NULL, NULL, NULL, napi_default, NULL},
+        {"intervalsRemove", NULL, intervals_remove, NULL, NULL, NULL, napi_default, NULL},
+        {"intervalsOverlapping", NULL, intervals_overlapping, NULL, NULL, NULL, napi_default, NULL},
+        {"intervalsPositions", NULL, intervals_positions, NULL, NULL, NULL, napi_default, NULL},
         {"createDeli", NULL, create_deli, NULL, NULL, NULL, napi_default, NULL},
         {"deliTicket", NULL, deli_ticket, NULL, NULL, NULL, napi_default, NULL},
         {"deliError", NULL, deli_error, NULL, NULL, NULL, napi_default, NULL},
