@@ -78,6 +78,9 @@ extern "C" hipError_t mt_launch_refs_resolve_docs(const mt_gstate* g, const uint
 extern "C" hipError_t mt_launch_intervals_overlap(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
                                                   uint32_t n_docs, const uint32_t* row_ptr, uint32_t* counts,
                                                   uint32_t* out, hipStream_t st);
+extern "C" hipError_t mt_launch_text_ranges(const mt_gstate* g, const mt_text_query* q, uint32_t n, uint32_t n_docs,
+                                            const uint32_t* row_ptr, uint16_t* units, const uint32_t* m_row_ptr,
+                                            mt_text_marker* markers, mt_text_count* counts, hipStream_t st);
 extern "C" hipError_t mt_launch_intervals_claim(const mt_gstate* g, const mt_interval_add* in, const mt_pos_result* at,
                                                 uint32_t n, uint32_t n_docs, uint32_t* handles, hipStream_t st);
 extern "C" hipError_t mt_launch_intervals_release(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
@@ -1190,6 +1193,106 @@ mt_status mt_intervals_overlapping(mt_engine* e, const mt_interval_query* q, uin
         if (hipMemcpyAsync(drp, row_ptr, cb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
             (st = mt_intervals_overlapping_device(e, dq, n, drp, dc, dout)) != MT_OK ||
             hipMemcpyAsync(out, dout, sum * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            if (st == MT_OK) st = MT_ERR_HIP;
+        }
+    } while (0);
+    if (dout) (void)hipFree(dout);
+    (void)hipFree(buf);
+    return st;
+}
+
+mt_status mt_text_ranges_device(mt_engine* e, const mt_text_query* d_q, uint32_t n, const uint32_t* d_row_ptr,
+                                uint16_t* d_units, const uint32_t* d_m_row_ptr, mt_text_marker* d_markers,
+                                mt_text_count* d_counts) {
+    static_assert(sizeof(mt_text_query) == 32 && sizeof(mt_text_marker) == 8 && sizeof(mt_text_count) == 8,
+                  "mt_text_query is 32 bytes, mt_text_marker and mt_text_count 8");
+    if (!e || (n && (!d_q || !d_counts || (d_row_ptr && !d_units) || (d_m_row_ptr && (!d_row_ptr || !d_markers)))))
+        return MT_ERR_ARG;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_text_ranges(&e->g, d_q, n, e->n_docs, d_row_ptr, d_units, d_m_row_ptr, d_markers, d_counts, e->stream));
+    return MT_OK;
+}
+
+mt_status mt_text_lengths(mt_engine* e, const mt_text_query* q, uint32_t n, mt_text_count* out) {
+    if (!e || (n && (!q || !out))) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    uint8_t* buf = nullptr;
+    const size_t qb = (size_t)n * sizeof(mt_text_query), cb = (size_t)n * sizeof(mt_text_count);
+    if (hipMalloc(&buf, qb + cb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dq = reinterpret_cast<mt_text_query*>(buf);
+    auto* dc = reinterpret_cast<mt_text_count*>(buf + qb);
+    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = mt_launch_text_ranges(&e->g, dq, n, e->n_docs, nullptr, nullptr, nullptr, nullptr, dc, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(out, dc, cb, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    (void)hipFree(buf);
+    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+}
+
+mt_status mt_text_ranges(mt_engine* e, const mt_text_query* q, uint32_t n, uint32_t* row_ptr, uint16_t* units,
+                         uint64_t cap, uint32_t* m_row_ptr, mt_text_marker* markers, uint64_t m_cap, uint64_t* totals) {
+    if (!e || !row_ptr || !m_row_ptr || !totals || (n && !q)) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
+    row_ptr[0] = m_row_ptr[0] = 0;
+    totals[0] = totals[1] = 0;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    // the count pass, the rows' prefix sums on the host, then the write pass
+    uint8_t* buf = nullptr;
+    const size_t qb = (size_t)n * sizeof(mt_text_query), cb = (size_t)n * sizeof(mt_text_count);
+    const size_t rb = (((size_t)n + 1) * sizeof(uint32_t) + 15) & ~size_t(15);
+    if (hipMalloc(&buf, qb + cb + 2 * rb) != hipSuccess) return MT_ERR_NOMEM;
+    auto* dq = reinterpret_cast<mt_text_query*>(buf);
+    auto* dc = reinterpret_cast<mt_text_count*>(buf + qb);
+    auto* drp = reinterpret_cast<uint32_t*>(buf + qb + cb);
+    auto* dmrp = reinterpret_cast<uint32_t*>(buf + qb + cb + rb);
+    uint8_t* dout = nullptr;
+    mt_status st = MT_OK;
+    do {
+        std::vector<mt_text_count> cnt(n);
+        if (hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            (st = mt_text_ranges_device(e, dq, n, nullptr, nullptr, nullptr, nullptr, dc)) != MT_OK ||
+            hipMemcpyAsync(cnt.data(), dc, cb, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            if (st == MT_OK) st = MT_ERR_HIP;
+            break;
+        }
+        uint64_t sum = 0, msum = 0;
+        for (uint32_t i = 0; i < n && sum < (1ull << 32) && msum < (1ull << 32); i++) {
+            sum += cnt[i].units;
+            msum += cnt[i].markers;
+            row_ptr[i + 1] = (uint32_t)sum;
+            m_row_ptr[i + 1] = (uint32_t)msum;
+        }
+        if (sum >= (1ull << 32) || msum >= (1ull << 32)) {
+            st = MT_ERR_ARG;
+            break;
+        }
+        totals[0] = sum;
+        totals[1] = msum;
+        if (!units || sum + msum == 0) break;
+        if (cap < sum || m_cap < msum || (msum && !markers)) {
+            st = MT_ERR_ARG;
+            break;
+        }
+        const size_t ub = (sum * sizeof(uint16_t) + 15) & ~size_t(15), mb = msum * sizeof(mt_text_marker);
+        if (hipMalloc(&dout, ub + mb + 16) != hipSuccess) {
+            st = MT_ERR_NOMEM;
+            break;
+        }
+        auto* du = reinterpret_cast<uint16_t*>(dout);
+        auto* dm = reinterpret_cast<mt_text_marker*>(dout + ub);
+        if (hipMemcpyAsync(drp, row_ptr, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            hipMemcpyAsync(dmrp, m_row_ptr, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            (st = mt_text_ranges_device(e, dq, n, drp, du, dmrp, dm, dc)) != MT_OK ||
+            (sum && hipMemcpyAsync(units, du, sum * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
+            (msum && hipMemcpyAsync(markers, dm, mb, hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
             hipStreamSynchronize(e->stream) != hipSuccess) {
             if (st == MT_OK) st = MT_ERR_HIP;
         }

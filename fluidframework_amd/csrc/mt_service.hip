@@ -7,6 +7,7 @@
 #include "mt_checksum.h"
 #include "mt_seqwin.h"
 #include "mt_state.h"
+#include "mt_view.h"
 #include "mt_wave.h"
 
 // Client + startOrUpdateCollaboration: an empty root block, collab window (0, 0)
@@ -720,21 +721,8 @@ __global__ __launch_bounds__(64) void mt_resolve_kernel(mt_gstate g, const mt_po
     const mt_doc_scalars sc = g.sc[d];
     const int n = sc.nseg;
     const size_t so = (size_t)d * g.segcap;
-    const bool wdoc = (sc.wide & MT_WIDE_DOC) != 0;
-    const int form = mt_form(wdoc, sc.wide);
-    const bool local = qq.ref_seq == MT_POS_LOCAL;
-    const int32_t R = qq.ref_seq;
-    const uint32_t C = qq.client;
-    auto view_len = [&](int i) -> int {  // nodeLength's leaf branch (mergeTree.ts:1659-1697)
-        const bool rm = (g.flags[so + i] & MT_SF_REMOVED) != 0;
-        if (local) return rm ? 0 : (int)g.len[so + i];
-        // (pending local edits: seq / removedSeq -1, UnassignedSequenceNumber, seen by no refSeq)
-        const bool seen = mt_gclient(g, wdoc, so + i) == C || (g.seq[so + i] != -1 && g.seq[so + i] <= R);
-        const bool ov = C < 64 ? ((g.ovl[so + i] >> C) & 1ull) != 0
-                               : (wdoc && mt_ovx_has2(mt_govx_lo(g, so + i), mt_govx_hi(g, form, so + i), C));
-        const bool hid = rm && (mt_grclient(g, wdoc, so + i) == C || ov || (g.rseq[so + i] != -1 && g.rseq[so + i] <= R));
-        return (seen && !hid) ? (int)g.len[so + i] : 0;
-    };
+    const mt_view view = mt_view_of(sc, qq.ref_seq, qq.client);
+    auto view_len = [&](int i) -> int { return mt_view_len(g, view, so + i); };  // nodeLength's leaf branch (mt_view.h)
     mt_pos_result r{-1, 0, 0, 0};
     int vcarry = 0, lcarry = 0;
     const bool by_ord = qq.kind == MT_POS_OF_ORDINAL;

@@ -120,6 +120,12 @@ def lib():
                          ('mt_intervals_positions', [vp, vp, u32, vp])):
             getattr(L, name).argtypes = at
             getattr(L, name).restype = ctypes.c_int
+        for name, at in (('mt_text_ranges', [vp, vp, u32, vp, vp, u64, vp, vp, u64, vp]),
+                         ('mt_text_ranges_device', [vp, vp, u32, vp, vp, vp, vp, vp]),
+                         ('mt_text_lengths', [vp, vp, u32, vp])):
+            if hasattr(L, name):  # (absent from older A/B builds)
+                getattr(L, name).argtypes = at
+                getattr(L, name).restype = ctypes.c_int
         L.mt_version.restype = ctypes.c_char_p
         for name in ('mt_engine_create', 'mt_engine_destroy', 'mt_docs_init', 'mt_batch_upload', 'mt_batch_apply',
                      'mt_batch_free', 'mt_submit', 'mt_sync', 'mt_get_length', 'mt_get_text', 'mt_get_state',
@@ -491,6 +497,57 @@ class MergeEngine:
         out = np.zeros((len(d), self._iv_per_doc), dtype=INTERVAL_POS_DTYPE)
         _check(lib().mt_intervals_positions(self.h, _ptr(d), len(d), _ptr(out)), 'mt_intervals_positions')
         return out
+
+    # -- text reads (textSegment.ts:124-276; include/mtgpu.h "text reads") ------------------------
+    @staticmethod
+    def text_queries(docs, starts=0, ends=None, ref_seqs=None, clients=0, placeholders='', flags=0):
+        """textread.TEXT_QUERY_DTYPE rows.  ends None: past every view; ref_seqs None: the local view;
+        placeholders: '' or one UTF-16 unit each (a str for all, or a sequence)."""
+        from .textread import TEXT_END, TEXT_LOCAL, TEXT_QUERY_DTYPE
+        q = np.zeros(len(docs), dtype=TEXT_QUERY_DTYPE)
+        q['doc'], q['start'], q['client'], q['flags'] = docs, starts, clients, flags
+        q['end'] = TEXT_END if ends is None else ends
+        q['ref_seq'] = TEXT_LOCAL if ref_seqs is None else ref_seqs
+        ph = [placeholders] * len(q) if isinstance(placeholders, str) else placeholders
+        q['placeholder'] = [int.from_bytes(p.encode('utf-16-le', 'surrogatepass'), 'little') if p else 0 for p in ph]
+        return q
+
+    def text_ranges(self, queries):
+        """MergeTreeTextHelper.getText for a batch of textread.TEXT_QUERY_DTYPE rows (mt_text_ranges):
+        (texts, markers) -- one str per query (UTF-16 units, surrogate halves kept) and, for the
+        queries with textread.TEXT_MARKERS, the visited markers as [(ordinal, out_offset), ...]."""
+        from .textread import TEXT_MARKER_DTYPE, TEXT_QUERY_DTYPE
+        q = np.ascontiguousarray(queries, dtype=TEXT_QUERY_DTYPE)
+        n = len(q)
+        rp, mrp = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+        totals = np.zeros(2, dtype=np.uint64)
+        args = (self.h, _ptr(q), n, _ptr(rp))
+        _check(lib().mt_text_ranges(*args, None, 0, _ptr(mrp), None, 0, _ptr(totals)), 'mt_text_ranges')  # (the counts alone)
+        units = np.zeros(int(totals[0]), dtype='<u2')
+        marks = np.zeros(int(totals[1]), dtype=TEXT_MARKER_DTYPE)
+        if len(units) or len(marks):
+            _check(lib().mt_text_ranges(*args, _ptr(units), len(units), _ptr(mrp), _ptr(marks), len(marks), _ptr(totals)),
+                   'mt_text_ranges')
+        raw = units.tobytes()
+        texts = [raw[2 * int(rp[i]):2 * int(rp[i + 1])].decode('utf-16-le', 'surrogatepass') for i in range(n)]
+        markers = [[(int(m['ordinal']), int(m['out_offset'])) for m in marks[mrp[i]:mrp[i + 1]]] for i in range(n)]
+        return texts, markers
+
+    def text_lengths(self, queries):
+        """The count pass alone (mt_text_lengths): textread.TEXT_COUNT_DTYPE rows -- each answer's units
+        (with a placeholder over the whole range: MergeTree.getLength of the view) and marker rows."""
+        from .textread import TEXT_COUNT_DTYPE, TEXT_QUERY_DTYPE
+        q = np.ascontiguousarray(queries, dtype=TEXT_QUERY_DTYPE)
+        out = np.zeros(len(q), dtype=TEXT_COUNT_DTYPE)
+        _check(lib().mt_text_lengths(self.h, _ptr(q), len(q), _ptr(out)), 'mt_text_lengths')
+        return out
+
+    def text_ranges_device(self, d_queries, n, d_row_ptr, d_units, d_m_row_ptr, d_markers, d_counts):
+        """mt_text_ranges_device: device pointers (ints; d_row_ptr 0 for the count pass, d_m_row_ptr 0 for
+        no marker rows); complete after the sync done here."""
+        _check(lib().mt_text_ranges_device(self.h, d_queries, n, d_row_ptr or None, d_units or None, d_m_row_ptr or None,
+                                           d_markers or None, d_counts), 'mt_text_ranges_device')
+        _check(lib().mt_sync(self.h), 'mt_sync')
 
     # -- readout -------------------------------------------------------------------------
     def checksums(self):

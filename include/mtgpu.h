@@ -414,6 +414,66 @@ mt_status mt_segment_infos(mt_engine* eng, const uint32_t* docs, const int32_t* 
 /* a segment's text: `len` code units of document doc's arena at `toff` (from mt_seg_info) */
 mt_status mt_segment_text(mt_engine* eng, uint32_t doc, uint32_t toff, uint32_t len, uint16_t* out);
 
+/* ---- text reads --------------------------------------------------------------------------------
+ * MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start, end) and the walk under
+ * getTextAndMarkers (textSegment.ts:124-276; SharedString.getText and its siblings,
+ * sharedString.ts:207-229) for a batch of queries, one wave per query over the document's state in
+ * HBM: mapRange -> nodeMap (mergeTree.ts:2903-2965) with gatherText as the leaf action
+ * (textSegment.ts:188-275).  With p a leaf's exclusive prefix in the view and len > 0 its view length,
+ * the leaf is visited when end - p > 0 && start - p < len.  A visited text segment contributes the
+ * units [min(a, b), max(a, b)) of its text, a = clamp(start - p, 0, len), b = clamp(end - p, 0, len):
+ * String.substring, argument swap included, so a query with start > end is not empty when one segment
+ * spans both positions.  A visited marker contributes `placeholder` once (its cachedLength is 1) when
+ * that is non-zero, else nothing; with MT_TEXT_MARKERS every visited marker also appends a row
+ * {ordinal, out_offset} to the query's marker list, out_offset being the units of the answer before it.
+ * Leaves hidden in the view (length 0) contribute nothing.  start and end are taken as they are,
+ * negative ones included: the defaults (0, the view's length) are the caller's.  The view is
+ * (ref_seq, client) or, with ref_seq = MT_POS_LOCAL, the local view, exactly as for mt_pos_query.
+ * The answer is UTF-16 code units for narrow and wide documents alike.  The "*" placeholder of the
+ * reference ("\n" + Marker.toString()) and getTextAndMarkers' cut at labelled markers are composed by
+ * the caller from the text without placeholders plus the marker list. */
+#define MT_TEXT_MARKERS 1u                /* mt_text_query.flags: list the visited markers */
+#define MT_TEXT_BAD_QUERY 0xFFFFFFFFu     /* mt_text_count.units of a query the device refused */
+typedef struct mt_text_query {  /* 32 bytes */
+    uint32_t doc;
+    int32_t start, end;         /* the range in the view, unclamped */
+    int32_t ref_seq;            /* the view's refSeq, or MT_POS_LOCAL */
+    uint16_t client;            /* the view's short client id (ignored for MT_POS_LOCAL) */
+    uint16_t placeholder;       /* one UTF-16 unit written per visited marker, 0: none */
+    uint32_t flags;             /* MT_TEXT_MARKERS */
+    uint32_t reserved[2];       /* 0 */
+} mt_text_query;
+typedef struct mt_text_marker { /* 8 bytes */
+    int32_t ordinal;            /* the marker's index among the linked segments (mt_segment_infos) */
+    uint32_t out_offset;        /* units of the query's answer written before it */
+} mt_text_marker;
+typedef struct mt_text_count {  /* 8 bytes */
+    uint32_t units;             /* the answer's length in units; MT_TEXT_BAD_QUERY */
+    uint32_t markers;           /* its marker rows (0 without MT_TEXT_MARKERS) */
+} mt_text_count;
+/* Two passes, as mt_intervals_overlapping: a count pass, the rows' prefix sums on the host, a write
+ * pass.  Query i's units are units[row_ptr[i] .. row_ptr[i+1]) and its marker rows
+ * markers[m_row_ptr[i] .. m_row_ptr[i+1]) (both row_ptr arrays: n + 1 entries; totals[0] / totals[1]:
+ * all units / all marker rows).  With units == NULL only the row_ptr arrays and totals are filled;
+ * cap below totals[0], or m_cap below totals[1], is MT_ERR_ARG.  Stream-ordered after every submitted
+ * op; a document with a sticky error answers from its state before the failing message. */
+mt_status mt_text_ranges(mt_engine* eng, const mt_text_query* q, uint32_t n, uint32_t* row_ptr, uint16_t* units,
+                         uint64_t cap, uint32_t* m_row_ptr, mt_text_marker* markers, uint64_t m_cap, uint64_t* totals);
+/* the same with device-resident arguments (asynchronous on the engine's stream).  d_row_ptr == NULL:
+ * the count pass, d_counts[i] = query i's counts.  Else the write pass: query i's units go to
+ * d_units[d_row_ptr[i] ..), at most d_row_ptr[i+1] - d_row_ptr[i] of them, its marker rows to
+ * d_markers[d_m_row_ptr[i] ..) likewise (d_m_row_ptr == NULL: no marker rows are written), and
+ * d_counts[i] is still the whole count -- rows from a count pass's prefix sums, or rows of a capacity
+ * the caller chose; nothing is written past a row.  A query the host could not check (doc >= n_docs)
+ * gets units = MT_TEXT_BAD_QUERY and reads nothing. */
+mt_status mt_text_ranges_device(mt_engine* eng, const mt_text_query* d_q, uint32_t n, const uint32_t* d_row_ptr,
+                                uint16_t* d_units, const uint32_t* d_m_row_ptr, mt_text_marker* d_markers,
+                                mt_text_count* d_counts);
+/* the count pass alone: out[i] = query i's counts.  Over the whole range (start 0, end INT32_MAX) with
+ * a placeholder, units is MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1577-1579); without
+ * one, that less the view's markers. */
+mt_status mt_text_lengths(mt_engine* eng, const mt_text_query* q, uint32_t n, mt_text_count* out);
+
 /* The ops document `doc` regenerated at its MT_SEQ_REGEN records since the last drain (at most 256
  * records / 4 KiB of payload between drains, else MT_DERR_CAPACITY): per regenerated op one
  * MT_OP_NOOP header record whose seq is the index of the resetting record within the document's

@@ -30,6 +30,7 @@ const path = require("path");
 const native = require(path.join(__dirname, "mtgpu.node"));
 const { LocalReference, ReferenceType, REF_NONE, REF_FULL } = require(path.join(__dirname, "localReference.js"));
 const { IntervalCollection, IntervalType } = require(path.join(__dirname, "intervalCollection.js"));
+const { TextHelper } = require(path.join(__dirname, "textHelper.js"));
 
 const INSERT = 0, REMOVE = 1, ANNOTATE = 2, GROUP = 3, NOOP = 3;
 const F_REWRITE = 1, F_PROPS = 2, F_GROUP_MORE = 4, F_MARKER = 128;
@@ -485,7 +486,31 @@ class BatchClient {
         }
     }
 
-    getText() { this.engine.flush(); this._checkError(); return native.getText(this.engine.handle, this.doc); }
+    // ---- SharedString's text readers (sharedString.ts:207-229) over createTextHelper(): each is one
+    // batched device read in the client's own view (js/textHelper.js; include/mtgpu.h "text reads")
+    /** Client.createTextHelper (client.ts:895-897): getText / getTextAndMarkers in any view */
+    createTextHelper() { return new TextHelper(this); }
+    _textHelper() { return this._helper || (this._helper = this.createTextHelper()); }
+    /** SharedString.getText(start?, end?); without arguments the whole-document read (mt_get_text) */
+    getText(start, end) {
+        if (start === undefined && end === undefined) {
+            this.engine.flush();
+            this._checkError();
+            return native.getText(this.engine.handle, this.doc);
+        }
+        return this._textHelper().getText(this.getCurrentSeq(), this.getClientId(), "", start, end);
+    }
+    /** SharedString.getTextWithPlaceholders: a space for every marker */
+    getTextWithPlaceholders() { return this._textHelper().getText(this.getCurrentSeq(), this.getClientId(), " "); }
+    getTextRangeWithPlaceholders(start, end) {
+        return this._textHelper().getText(this.getCurrentSeq(), this.getClientId(), " ", start, end);
+    }
+    /** SharedString.getTextRangeWithMarkers: "\n" + marker.toString() for every marker */
+    getTextRangeWithMarkers(start, end) {
+        return this._textHelper().getText(this.getCurrentSeq(), this.getClientId(), "*", start, end);
+    }
+    /** SharedString.getTextAndMarkers(label): {parallelText, parallelMarkers} (markers as segment descriptors) */
+    getTextAndMarkers(label) { return this._textHelper().getTextAndMarkers(this.getCurrentSeq(), this.getClientId(), label); }
 
     /**
      * Client.findTile (client.ts:1073-1076): the tile holding `tileLabel` in its
@@ -860,4 +885,4 @@ class BatchClient {
     }
 }
 
-module.exports = { BatchEngine, BatchClient, LocalReference, ReferenceType, IntervalCollection, IntervalType, native };
+module.exports = { BatchEngine, BatchClient, LocalReference, ReferenceType, IntervalCollection, IntervalType, TextHelper, native };

@@ -680,6 +680,45 @@ static napi_value intervals_overlapping(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* textRanges(engine, queries (32-byte mt_text_query rows)) -> [Buffer of u16 units, Buffer of n + 1 u32
+ * row pointers, Buffer of 8-byte mt_text_marker rows, Buffer of n + 1 u32 marker row pointers] */
+static napi_value text_ranges(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], out, bu, brp, bm, bmrp;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 2 ? get_box(env, argv[0]) : NULL;
+    size_t nq = 0;
+    const void* q = b ? buffer_data(env, argv[1], &nq) : NULL;
+    if (!b || nq % sizeof(mt_text_query)) {
+        napi_throw_type_error(env, NULL, "textRanges(engine, queries)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(nq / sizeof(mt_text_query));
+    void *rows = NULL, *mrows = NULL, *units = NULL, *marks = NULL;
+    uint64_t totals[2] = {0, 0};
+    NAPI_CALL(env, napi_create_buffer(env, ((size_t)n + 1) * sizeof(uint32_t), &rows, &brp));
+    NAPI_CALL(env, napi_create_buffer(env, ((size_t)n + 1) * sizeof(uint32_t), &mrows, &bmrp));
+    enter(b);
+    mt_status st = mt_text_ranges(b->e, (const mt_text_query*)q, n, (uint32_t*)rows, NULL, 0, (uint32_t*)mrows, NULL, 0, totals);
+    leave(b);
+    if (st) return throw_status(env, "mt_text_ranges", st);
+    NAPI_CALL(env, napi_create_buffer(env, totals[0] ? totals[0] * sizeof(uint16_t) : 1, &units, &bu));
+    NAPI_CALL(env, napi_create_buffer(env, totals[1] ? totals[1] * sizeof(mt_text_marker) : 1, &marks, &bm));
+    if (totals[0] || totals[1]) {
+        enter(b);
+        st = mt_text_ranges(b->e, (const mt_text_query*)q, n, (uint32_t*)rows, (uint16_t*)units, totals[0], (uint32_t*)mrows,
+                            (mt_text_marker*)marks, totals[1], totals);
+        leave(b);
+        if (st) return throw_status(env, "mt_text_ranges", st);
+    }
+    NAPI_CALL(env, napi_create_array_with_length(env, 4, &out));
+    NAPI_CALL(env, napi_set_element(env, out, 0, bu));
+    NAPI_CALL(env, napi_set_element(env, out, 1, brp));
+    NAPI_CALL(env, napi_set_element(env, out, 2, bm));
+    NAPI_CALL(env, napi_set_element(env, out, 3, bmrp));
+    return out;
+}
+
 /* intervalsPositions(engine, docs (u32 rows), perDoc) -> Buffer of docs x perDoc 24-byte mt_interval_pos rows */
 static napi_value intervals_positions(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -865,6 +904,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"intervalsRemove", NULL, intervals_remove, NULL, NULL, NULL, napi_default, NULL},
         {"intervalsOverlapping", NULL, intervals_overlapping, NULL, NULL, NULL, napi_default, NULL},
         {"intervalsPositions", NULL, intervals_positions, NULL, NULL, NULL, napi_default, NULL},
+        {"textRanges", NULL, text_ranges, NULL, NULL, NULL, napi_default, NULL},
         {"createDeli", NULL, create_deli, NULL, NULL, NULL, napi_default, NULL},
         {"deliTicket", NULL, deli_ticket, NULL, NULL, NULL, napi_default, NULL},
         {"deliError", NULL, deli_error, NULL, NULL, NULL, napi_default, NULL},
