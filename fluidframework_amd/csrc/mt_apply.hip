@@ -20,6 +20,7 @@
 
 #include "../../include/mtgpu.h"
 #include "mt_checksum.h"
+#include "mt_launch.h"
 #include "mt_state.h"
 #include "mt_synth.h"
 #include "mt_wave.h"

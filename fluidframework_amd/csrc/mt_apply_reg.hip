@@ -32,6 +32,7 @@
 
 #include "../../include/mtgpu.h"
 #include "mt_seqwin.h"
+#include "mt_launch.h"
 #include "mt_state.h"
 #include "mt_wave.h"
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mtgpu.h"
+#include "mt_launch.h"
 #include "mt_wave.h"
 
 namespace mtd {

@@ -5,140 +5,33 @@
 // at most `ops_per_launch` ops per document (the serving tick; 0 = the whole batch in one
 // launch).  Before every launch the documents with work are binned by the LDS capacity class
 // they need (mt_bin_kernel), so small documents run at high occupancy.
-#include <hip/hip_runtime.h>
-
+//
+// This file: engine lifecycle, pools, document init / load, label keys, batches, the apply scheduler,
+// the tick ring, mt_log_to_ticks*, synthetic generation and the statistics.  The query entry points
+// are in mt_queries.cpp, the canonical readout in mt_readout.cpp; what the three share is in
+// mt_engine_impl.h.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/mtgpu.h"
 #include "mt_checksum.h"
-#include "mt_state.h"
-
-extern "C" hipError_t mt_launch_apply(int cap_class, const mt_gstate* g, const mt_op_rec* ops, const uint8_t* payload,
-                                      const uint32_t* row_ptr, const uint32_t* doc_ids, uint32_t n_docs,
-                                      uint32_t op_lo, uint32_t op_cnt, hipStream_t stream);
-extern "C" hipError_t mt_launch_apply_reg(int cap_class, int form, const mt_gstate* g, const mt_op_rec* ops,
-                                          const uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
-                                          uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, hipStream_t stream);
-extern "C" size_t mt_lds_bytes(int cap_class);
-extern "C" hipError_t mt_launch_apply_loc(int cap_class, const mt_gstate* g, const mt_op_rec* ops, const uint8_t* payload,
-                                          const uint32_t* row_ptr, const uint32_t* doc_ids, uint32_t n_docs,
-                                          uint32_t op_lo, uint32_t op_cnt, hipStream_t stream);
-extern "C" hipError_t mt_launch_apply_big(int cap_class, const mt_gstate* g, const mt_op_rec* ops,
-                                          const uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
-                                          uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, uint8_t* ws,
-                                          hipStream_t stream);
-extern "C" hipError_t mt_launch_apply_wide(int cap_class, const mt_gstate* g, const mt_op_rec* ops,
-                                           const uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
-                                           uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, uint8_t* ws, int xl,
-                                           hipStream_t stream);
-extern "C" size_t mt_lds_bytes_wide(int cap_class);
-extern "C" hipError_t mt_launch_apply_loc_big(int cap_class, int gw, const mt_gstate* g, const mt_op_rec* ops,
-                                              const uint8_t* payload, const uint32_t* row_ptr,
-                                              const uint32_t* doc_ids, uint32_t n_docs, uint32_t op_lo,
-                                              uint32_t op_cnt, uint8_t* ws, hipStream_t stream);
-extern "C" size_t mt_lds_bytes_loc(int cap_class, int gw);
-extern "C" hipError_t mt_launch_init(const mt_gstate* g, uint32_t n_docs, hipStream_t st);
-extern "C" hipError_t mt_launch_label_keys(const mt_gstate* g, uint32_t d0, uint32_t d1, uint32_t keys, hipStream_t st);
-extern "C" hipError_t mt_launch_load(const mt_gstate* g, uint32_t n, const uint32_t* doc_ids, const uint32_t* row_ptr,
-                                     const mt_load_seg* segs, const uint8_t* text, const int32_t* min_seq,
-                                     const int32_t* cur_seq, hipStream_t st);
-extern "C" hipError_t mt_launch_bin(const mt_gstate* g, const uint32_t* row_ptr, uint32_t n_docs, uint32_t op_lo,
-                                    uint32_t op_cnt, const int32_t* classes, int n_classes, int first_lds,
-                                    int first_wide, uint32_t* counts, uint32_t* ids, const mt_op_rec* ops,
-                                    const uint8_t* payload, unsigned long long* acc, hipStream_t st);
-extern "C" hipError_t mt_launch_checksum(const mt_gstate* g, uint32_t n_docs, uint64_t* out, hipStream_t st);
-extern "C" hipError_t mt_launch_stacks(const mt_gstate* g, const mt_tile_query* q, uint32_t n, uint32_t cap,
-                                       mt_stack_item* items, uint32_t* depth, hipStream_t st);
-extern "C" hipError_t mt_launch_tiles(const mt_gstate* g, const mt_tile_query* q, uint32_t n, mt_tile_result* out,
-                                      hipStream_t st);
-extern "C" hipError_t mt_launch_resolve(const mt_gstate* g, const mt_pos_query* q, uint32_t n, uint32_t n_docs,
-                                        mt_pos_result* out,
-                                        hipStream_t st);
-extern "C" hipError_t mt_launch_seginfo(const mt_gstate* g, const uint32_t* docs, const int32_t* ords, uint32_t n,
-                                        mt_seg_info* out, hipStream_t st);
-extern "C" hipError_t mt_launch_events_pack(const mt_gstate* g, uint32_t n_docs, const uint64_t* off, mt_event* out,
-                                            hipStream_t st);
-extern "C" hipError_t mt_launch_refs_track(const mt_gstate* g, uint32_t n_docs, hipStream_t st);
-extern "C" hipError_t mt_launch_refs_claim(const mt_gstate* g, const mt_ref_add* in, const mt_pos_result* at, uint32_t n,
-                                           uint32_t n_docs, uint32_t* handles, hipStream_t st);
-extern "C" hipError_t mt_launch_refs_release(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
-                                             uint32_t n_docs, hipStream_t st);
-extern "C" hipError_t mt_launch_refs_free_docs(const mt_gstate* g, const uint32_t* ids, uint32_t n, uint32_t n_docs,
-                                               hipStream_t st);
-extern "C" hipError_t mt_launch_refs_resolve_docs(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
-                                                  hipStream_t st);
-extern "C" hipError_t mt_launch_intervals_overlap(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
-                                                  uint32_t n_docs, const uint32_t* row_ptr, uint32_t* counts,
-                                                  uint32_t* out, hipStream_t st);
-extern "C" hipError_t mt_launch_text_ranges(const mt_gstate* g, const mt_text_query* q, uint32_t n, uint32_t n_docs,
-                                            const uint32_t* row_ptr, uint16_t* units, const uint32_t* m_row_ptr,
-                                            mt_text_marker* markers, mt_text_count* counts, hipStream_t st);
-extern "C" hipError_t mt_launch_intervals_claim(const mt_gstate* g, const mt_interval_add* in, const mt_pos_result* at,
-                                                uint32_t n, uint32_t n_docs, uint32_t* handles, hipStream_t st);
-extern "C" hipError_t mt_launch_intervals_release(const mt_gstate* g, const mt_interval_query* q, uint32_t n,
-                                                  uint32_t n_docs, uint32_t* removed, hipStream_t st);
-extern "C" hipError_t mt_launch_intervals_free_docs(const mt_gstate* g, const uint32_t* ids, uint32_t n, uint32_t n_docs,
-                                                    hipStream_t st);
-extern "C" hipError_t mt_launch_intervals_gather(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
-                                                 mt_interval_pos* out, hipStream_t st);
-extern "C" hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
-                                               uint32_t n_docs, mt_ref_pos* out, hipStream_t st);
-extern "C" hipError_t mt_launch_fixup(const mt_gstate* g, const mt_op_rec* ops, uint32_t n_docs, hipStream_t st);
-extern "C" hipError_t mt_launch_scan_records(const mt_op_rec* ops, uint64_t n_ops, uint64_t payload_bytes,
-                                             uint32_t* flags, hipStream_t st);
-extern "C" hipError_t mt_launch_snapshot(const mt_gstate* g, uint32_t d0, uint32_t n_docs, uint32_t cap,
-                                         uint32_t* specs, uint32_t* counts, hipStream_t st);
-extern "C" hipError_t mt_launch_gen(int cap_class, const mt_gstate* g, const mt_synth_cfg* cfg, uint32_t doc_id_base,
-                                    const uint32_t* gids, int32_t* cref,
-                                    int32_t* stall, uint32_t* pay_used, uint32_t paycap, mt_op_rec* ops,
-                                    uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
-                                    uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, hipStream_t stream);
+#include "mt_engine_impl.h"
+#include "mt_scratch.h"
 
 namespace {
-// register engine <= 1024, LDS engine 2048, the LDS engine's HBM-workspace form above (only the
-// classes with CAP <= the engine's seg_capacity are used: mt_engine::n_classes)
+// The apply scheduler's tables (the counts that size them: mt_engine_impl.h).
 // (the register classes step by 64 slots -- K = 2 ... 16 registers per field -- so a document pays
 // for the slots it can reach in a launch, not for the next power of two)
 // (the largest class is 64 K - 64 slots: the LDS engine's slot indices and the heap's positions
 // between launches are u16, 0xFFFF being MT_DEAD_SLOT)
-const int32_t kClasses[] = {128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024,
-                            2048, 4096, 8192, 16384, 32768, 65472};
-constexpr int kNumClasses = 21;
-constexpr int kLdsClasses = 16;  // classes an LDS-resident kernel serves (the generator's)
-constexpr int kFirstLds = 15;    // index of the 2048 class: the first the register engine does not serve
-constexpr int kMaxSegCap = 65472;  // (the LDS engine's slot indices are u16: Lds::order / hslot)
-// bins of a tick (mt_bin_kernel): the classes, the editing documents, and the wide documents of the
-// classes from 2048 up (the LDS engine's wide form, include/mtgpu.h "limits")
-// the wide form serves the classes from 256 segments on: up to 512 staged in LDS, above in the HBM
-// workspace (mt_launch_apply_wide)
-constexpr int kFirstWide = 2;
-constexpr int kWideClasses = kNumClasses - kFirstWide;
-// ... and, after those, per register class: the documents that need the LDS engine there (declared
-// label keys), run by the LDS engine at that class's capacity, then the documents with client ids
-// above 32, run by the register engine's C64 form (mt_bin_kernel)
-// (then the editing documents that fit 256 / 512 slots: the editing form at that size; then those
-// above MT_LOC_CAP = 1024: its HBM-workspace form at 2048 / 4096; then those past 64 pending edits
-// (MT_WIDE_GROUPS): the HBM-workspace form with 4 group-mask words per slot at 1024 / 4096; then
-// both forms at 8192)
-constexpr int kLocForms = 8;
+const int32_t kClasses[kNumClasses] = {128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024,
+                                       2048, 4096, 8192, 16384, 32768, 65472};
+// the editing forms' capacities and group-mask words per slot (kLocForms, mt_engine_impl.h)
 const int32_t kLocCaps[kLocForms] = {256, 512, 2048, 4096, 1024, 4096, 8192, 8192};
 const int32_t kLocGW[kLocForms] = {1, 1, 1, 1, MT_LOC_GW, MT_LOC_GW, 1, MT_LOC_GW};
-constexpr int kBuckets = kNumClasses + 1 + kWideClasses + 2 * kFirstLds + kLocForms;
-// binning's counters: one per bucket, then per wide bucket the documents that stage the wide form's
-// extension (mt_state.h MT_WIDE_XK / MT_WIDE_XO) -- their launch takes an HBM region for it
-constexpr int kCounts = kBuckets + kWideClasses;
-// per-class statistics: the classes, the editing bucket, the LDS engine inside each register class,
-// the register engine's C64 form per class, the other editing forms
-constexpr int kStatClasses = kNumClasses + 1 + 2 * kFirstLds + kLocForms + kWideClasses;
-constexpr int kStatWide = kNumClasses + 1 + 2 * kFirstLds + kLocForms;  // the wide form's entries
 // {CAP, LB, IB, H} per class: at most mt::Lds<lds_cap(CAP)>'s and mtr::RLds<CAP/64>'s (the 128 and 192
 // classes take the 256 class's block and heap limits, which both hold: with CAP / 2 blocks and
 // CAP / 8 + 8 interior blocks no b = 32 launch fits them)
@@ -160,102 +53,7 @@ int lds_cap(int cap) {
 }
 }  // namespace
 
-struct mt_batch {
-    mt_op_rec* ops = nullptr;
-    uint8_t* payload = nullptr;
-    uint32_t* row_ptr = nullptr;
-    uint64_t n_ops = 0, payload_bytes = 0;
-    uint32_t n_docs = 0;
-    uint32_t max_ops_per_doc = 0;
-    bool wide = false;  // some record needs the wide form (its documents' wide state is allocated first)
-};
-
-struct mt_engine {
-    mt_cfg cfg{};
-    hipStream_t stream = nullptr;
-    mt_gstate g{};
-    uint32_t n_docs = 0;
-    std::vector<void*> allocs;
-    int32_t* d_classes = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint32_t* d_ids = nullptr;
-    uint32_t* h_counts = nullptr;  // pinned
-    unsigned long long* d_acc = nullptr;
-    std::vector<hipEvent_t> kev;   // per apply launch: start/stop pairs
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = 0.f, last_wall_ms = 0.f;
-    // per capacity class, plus one entry for the editing documents' bucket (index kNumClasses)
-    float cls_ms[kStatClasses] = {0};
-    uint32_t cls_launches[kStatClasses] = {0};
-    uint64_t cls_bytes[kStatClasses] = {0};
-    std::vector<int> kev_cls;
-    uint32_t last_launches = 0;
-    uint64_t last_bytes = 0;
-    // register-resident engine (mt_apply_reg.hip) for classes up to kRegMaxCap segments; the
-    // LDS engine (mt_apply.hip) above that, or everywhere with MTGPU_ENGINE=lds
-    bool use_reg = true;
-    bool reg_default = true;       // use_reg when not recording delta events (mt_events_enable)
-    int n_classes = kLdsClasses;   // classes with CAP <= seg_capacity
-    int first_lds = kFirstLds;     // first class not served by the register engine
-    uint8_t* ws = nullptr;         // HBM workspace of the classes above 2048 segments
-    size_t ws_bytes = 0;
-    // the capacity classes of one tick touch disjoint documents: each runs on its own stream
-    // (fork/join around the tick) so the small classes and every class's tail overlap;
-    // MTGPU_SERIAL=1 keeps them on the engine stream, one after another
-    bool concurrent = true;
-    bool desc_order = true;  // class kernels launched largest capacity first (see apply_launches)
-    hipStream_t side[kNumClasses] = {};
-    hipEvent_t fork_ev = nullptr, join_ev[kNumClasses] = {};
-    uint64_t gen = 0;  // bumped by every call that can change document state (snap_cache's key)
-    std::vector<uint16_t> lkeys;  // per document: its declared label keys (mt_set_label_keys), host copy
-    // the editing documents' pool rows (mt_state.h locbig / locgx): host copies, rows in use, rows held
-    std::vector<uint32_t> h_locbig, h_locgx, h_bucket;
-    uint32_t nbig = 0, bigcap = 0, ngx = 0, gxcap = 0;
-    std::vector<uint32_t> free_big, free_gx;  // rows given back by reloaded documents, reused first
-    // mt_submit_ticks: a ring of device slots; tick k is copied into slot k % kRing on the h2d
-    // stream while the ticks before it apply, and the slot is reused once its tick has applied (and
-    // its tickets have gone back on the d2h stream)
-    struct TickSlot {
-        mt_op_rec* ops = nullptr;
-        uint8_t* pay = nullptr;
-        uint32_t* rp = nullptr;
-        mt_raw_msg* msgs = nullptr;
-        uint32_t* mrp = nullptr;
-        mt_ticket* tk = nullptr;
-        uint64_t ops_cap = 0, pay_cap = 0, msg_cap = 0;
-        hipEvent_t ready = nullptr, applied = nullptr, drained = nullptr, ticketed = nullptr;
-    } ring[6];
-    hipStream_t h2d = nullptr, d2h = nullptr;
-    uint32_t* d_scan = nullptr;  // the first tick's record check on the device (mt_scan_records_kernel)
-    struct {  // mt_get_snapshots: the JSON of the last sizing call
-        bool valid = false;
-        uint64_t gen = 0;
-        uint32_t d0 = 0, n = 0, chunk = 0, n_names = 0;
-        const char* const* names = nullptr;
-        std::string json;
-        std::vector<uint64_t> off;
-    } snap_cache;
-};
 static constexpr int32_t kRegMaxCap = 1024;
-
-#define HIP_OK(x)                                                                                            \
-    do {                                                                                                     \
-        hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) {                                                                              \
-            fprintf(stderr, "libmtgpu: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MT_ERR_HIP;                                                                               \
-        }                                                                                                    \
-    } while (0)
-
-template <class T>
-static mt_status dalloc(mt_engine* e, T** p, size_t count) {
-    void* q = nullptr;
-    if (count == 0) count = 1;
-    if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) return MT_ERR_NOMEM;
-    e->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return MT_OK;
-}
 
 // The wide documents' extra per-segment state (mt_state.h), allocated for every document the first
 // time an engine sees wide content (a wide record or snapshot segment)
@@ -545,38 +343,6 @@ mt_status mt_engine_create(const mt_cfg* cfg, mt_engine** out) {
     return MT_OK;
 }
 
-// the interval tables (mt_intervals_enable)
-static void intervals_free(mt_engine* e) {
-    if (e->g.ivs) (void)hipFree(e->g.ivs);
-    if (e->g.ivn) (void)hipFree(e->g.ivn);
-    e->g.ivs = nullptr;
-    e->g.ivn = nullptr;
-    e->g.ivcap = 0;
-}
-// the local-reference tables (mt_refs_enable), and the intervals that rest on them
-static void refs_free(mt_engine* e) {
-    intervals_free(e);
-    for (void* p : {(void*)e->g.refs, (void*)e->g.refpos, (void*)e->g.refcur, (void*)e->g.refn, (void*)e->g.refq,
-                    (void*)e->g.refdrop})
-        if (p) (void)hipFree(p);
-    e->g.refs = nullptr;
-    e->g.refpos = nullptr;
-    e->g.refcur = e->g.refn = e->g.refq = e->g.refdrop = nullptr;
-    e->g.refcap = 0;
-}
-// every document's references freed, cursors at the start of the event buffer
-static hipError_t refs_clear(mt_engine* e) {
-    if (!e->g.refs) return hipSuccess;
-    const size_t D = e->cfg.max_docs;
-    hipError_t r = hipMemsetAsync(e->g.refs, 0, D * 2 * e->g.refcap * sizeof(mt_ref), e->stream);
-    if (r == hipSuccess) r = hipMemsetAsync(e->g.refcur, 0, D * sizeof(uint32_t), e->stream);
-    if (r == hipSuccess) r = hipMemsetAsync(e->g.refn, 0, D * sizeof(uint32_t), e->stream);
-    if (r == hipSuccess) r = hipMemsetAsync(e->g.refq, 0, D * sizeof(uint32_t), e->stream);
-    if (r == hipSuccess) r = hipMemsetAsync(e->g.refdrop, 0, D * sizeof(uint32_t), e->stream);
-    if (r == hipSuccess && e->g.ivs) r = mt_launch_intervals_free_docs(&e->g, nullptr, e->cfg.max_docs, e->cfg.max_docs, e->stream);
-    return r;
-}
-
 mt_status mt_engine_destroy(mt_engine* e) {
     if (!e) return MT_ERR_ARG;
     hipSetDevice(e->cfg.device);
@@ -715,612 +481,20 @@ mt_status mt_docs_load(mt_engine* e, uint32_t n, const uint32_t* doc_ids, const 
     // one staging allocation: ids, rebased row pointers, windows, segments, text
     std::vector<uint32_t> rp(n + 1);
     for (uint32_t i = 0; i <= n; i++) rp[i] = seg_row_ptr[i] - seg_row_ptr[0];
-    const size_t o_ids = 0, o_rp = o_ids + 4ull * n, o_mn = o_rp + 4ull * (n + 1), o_cs = o_mn + 4ull * n;
-    const size_t o_sg = (o_cs + 4ull * n + 31) & ~size_t(31), o_tx = o_sg + sizeof(mt_load_seg) * n_segs;
-    const size_t total = o_tx + text_bytes;
-    uint8_t* buf = nullptr;
-    if (hipMalloc(&buf, total ? total : 1) != hipSuccess) return MT_ERR_NOMEM;
-    mt_status st = MT_OK;
-    do {
-        if (hipMemcpyAsync(buf + o_ids, doc_ids, 4ull * n, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(buf + o_rp, rp.data(), 4ull * (n + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(buf + o_mn, min_seq, 4ull * n, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(buf + o_cs, cur_seq, 4ull * n, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            (n_segs && hipMemcpyAsync(buf + o_sg, segs + seg_row_ptr[0], sizeof(mt_load_seg) * n_segs,
-                                      hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
-            (text_bytes && hipMemcpyAsync(buf + o_tx, text, text_bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess)) {
-            st = MT_ERR_HIP;
-            break;
-        }
-        if (mt_launch_load(&e->g, n, reinterpret_cast<uint32_t*>(buf + o_ids), reinterpret_cast<uint32_t*>(buf + o_rp),
-                           reinterpret_cast<mt_load_seg*>(buf + o_sg), buf + o_tx, reinterpret_cast<int32_t*>(buf + o_mn),
-                           reinterpret_cast<int32_t*>(buf + o_cs), e->stream) != hipSuccess ||
-            mt_launch_refs_free_docs(&e->g, reinterpret_cast<uint32_t*>(buf + o_ids), n, e->n_docs, e->stream) != hipSuccess ||
-            mt_launch_intervals_free_docs(&e->g, reinterpret_cast<uint32_t*>(buf + o_ids), n, e->n_docs, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            st = MT_ERR_HIP;
-    } while (0);
-    hipFree(buf);
-    return st;
-}
-
-mt_status mt_find_tiles(mt_engine* e, const mt_tile_query* q, uint32_t n, mt_tile_result* out) {
-    static_assert(sizeof(mt_tile_query) == 48, "mt_tile_query is 48 bytes");
-    if (!e || (n && (!q || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    void* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_tile_query), rb = (size_t)n * sizeof(mt_tile_result);
-    if (hipMalloc(&buf, qb + rb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = static_cast<mt_tile_query*>(buf);
-    auto* dr = reinterpret_cast<mt_tile_result*>(static_cast<uint8_t*>(buf) + qb);
-    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_tiles(&e->g, dq, n, dr, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, dr, rb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_resolve_positions(mt_engine* e, const mt_pos_query* q, uint32_t n, mt_pos_result* out) {
-    static_assert(sizeof(mt_pos_query) == 16 && sizeof(mt_pos_result) == 16, "mt_pos_query / result are 16 bytes");
-    if (!e || (n && (!q || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs || q[i].kind > MT_POS_OF_ORDINAL) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    void* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_pos_query), rb = (size_t)n * sizeof(mt_pos_result);
-    if (hipMalloc(&buf, qb + rb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = static_cast<mt_pos_query*>(buf);
-    auto* dr = reinterpret_cast<mt_pos_result*>(static_cast<uint8_t*>(buf) + qb);
-    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_resolve(&e->g, dq, n, e->n_docs, dr, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, dr, rb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_resolve_positions_device(mt_engine* e, const mt_pos_query* d_q, uint32_t n, mt_pos_result* d_out) {
-    if (!e || (n && (!d_q || !d_out))) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_resolve(&e->g, d_q, n, e->n_docs, d_out, e->stream));
-    return MT_OK;
-}
-
-mt_status mt_segment_infos(mt_engine* e, const uint32_t* docs, const int32_t* ordinals, uint32_t n, mt_seg_info* out) {
-    static_assert(sizeof(mt_seg_info) == 168, "mt_seg_info is 168 bytes");
-    if (!e || (n && (!docs || !ordinals || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    void* buf = nullptr;
-    const size_t db = (size_t)n * 4, ob = (size_t)n * sizeof(mt_seg_info);
-    if (hipMalloc(&buf, 2 * db + ob) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dd = static_cast<uint32_t*>(buf);
-    auto* dor = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(buf) + db);
-    auto* dout = reinterpret_cast<mt_seg_info*>(static_cast<uint8_t*>(buf) + 2 * db);
-    hipError_t r = hipMemcpyAsync(dd, docs, db, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(dor, ordinals, db, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_seginfo(&e->g, dd, dor, n, dout, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_segment_text(mt_engine* e, uint32_t doc, uint32_t toff, uint32_t len, uint16_t* out) {
-    if (!e || doc >= e->n_docs || (len && !out)) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    mt_doc_scalars sc;
-    HIP_OK(hipMemcpyAsync(&sc, e->g.sc + doc, sizeof sc, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if ((uint64_t)toff + len > sc.text_top) return MT_ERR_ARG;
-    if (!len) return MT_OK;
-    const size_t base = ((size_t)doc * 2 + sc.text_half) * e->g.textcap;
-    if (sc.wide & MT_WIDE_DOC) {
-        HIP_OK(hipMemcpy(out, e->g.text + base + (size_t)toff * 2, (size_t)len * 2, hipMemcpyDeviceToHost));
-        return MT_OK;
-    }
-    std::vector<uint8_t> b(len);
-    HIP_OK(hipMemcpy(b.data(), e->g.text + base + toff, len, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < len; i++) out[i] = b[i];
-    return MT_OK;
-}
-
-mt_status mt_regen_drain(mt_engine* e, uint32_t doc, mt_op_rec* recs, uint32_t cap, uint8_t* payload, uint32_t pcap,
-                         uint32_t* n, uint32_t* pn) {
-    if (!e || doc >= e->n_docs || !n || !pn) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    uint32_t cnt[2] = {0, 0};  // mt_loc::rgn, rgpn (adjacent)
-    HIP_OK(hipMemcpy(cnt, &e->g.loc[doc].rgn, sizeof cnt, hipMemcpyDeviceToHost));
-    *n = cnt[0];
-    *pn = cnt[1];
-    if (!recs) return MT_OK;  // sizes only
-    // a drain takes everything or nothing: buffers too small leave the records in place
-    if (cap < cnt[0] || (cnt[1] && (!payload || pcap < cnt[1]))) return MT_ERR_ARG;
-    if (cnt[0])
-        HIP_OK(hipMemcpy(recs, e->g.rg + (size_t)doc * MT_RG_RECS, cnt[0] * sizeof(mt_op_rec), hipMemcpyDeviceToHost));
-    if (cnt[1]) HIP_OK(hipMemcpy(payload, e->g.rgp + (size_t)doc * MT_RG_BYTES, cnt[1], hipMemcpyDeviceToHost));
-    HIP_OK(hipMemset(&e->g.loc[doc].rgn, 0, sizeof cnt));
-    return MT_OK;
-}
-
-mt_status mt_range_stacks(mt_engine* e, const mt_tile_query* q, uint32_t n, uint32_t cap, mt_stack_item* items,
-                          uint32_t* depth) {
-    static_assert(sizeof(mt_stack_item) == 12, "mt_stack_item is 12 bytes");
-    if (!e || (n && (!q || !depth || (cap && !items)))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    void* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_tile_query), ib = (size_t)n * cap * sizeof(mt_stack_item),
-                 db = (size_t)n * sizeof(uint32_t);
-    if (hipMalloc(&buf, qb + ib + db) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = static_cast<mt_tile_query*>(buf);
-    auto* di = reinterpret_cast<mt_stack_item*>(static_cast<uint8_t*>(buf) + qb);
-    auto* dd = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + qb + ib);
-    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_stacks(&e->g, dq, n, cap, di, dd, e->stream);
-    if (r == hipSuccess && ib) r = hipMemcpyAsync(items, di, ib, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(depth, dd, db, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_events_enable(mt_engine* e, uint32_t per_doc) {
-    static_assert(sizeof(mt_event) == 96, "mt_event is 96 bytes");
-    if (!e) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (e->g.ev) HIP_OK(hipFree(e->g.ev));
-    if (e->g.evn) HIP_OK(hipFree(e->g.evn));
-    refs_free(e);  // (they follow this buffer's rows)
-    e->g.ev = nullptr;
-    e->g.evn = nullptr;
-    e->g.evcap = 0;
-    // the register engine records events in its own kernels (mtr::reg_apply_kernel_ev; its C64
-    // documents on the LDS engine); MTGPU_EV_ENGINE=lds keeps every class on the LDS engine instead
-    const char* evw = getenv("MTGPU_EV_ENGINE");
-    e->use_reg = (per_doc && evw && strcmp(evw, "lds") == 0) ? false : e->reg_default;
-    e->first_lds = e->use_reg ? kFirstLds : 0;
-    if (!per_doc) return MT_OK;
-    const size_t D = e->cfg.max_docs;
-    if (hipMalloc(&e->g.ev, D * per_doc * sizeof(mt_event)) != hipSuccess ||
-        hipMalloc(&e->g.evn, D * sizeof(uint32_t)) != hipSuccess) {
-        if (e->g.ev) (void)hipFree(e->g.ev);
-        e->g.ev = nullptr;
-        e->g.evn = nullptr;
-        e->use_reg = e->reg_default;
-        e->first_lds = e->use_reg ? kFirstLds : 0;
-        return MT_ERR_NOMEM;
-    }
-    e->g.evcap = per_doc;
-    HIP_OK(hipMemset(e->g.evn, 0, D * sizeof(uint32_t)));
-    return MT_OK;
-}
-
-mt_status mt_events_drain(mt_engine* e, mt_event* out, uint64_t cap, uint32_t* row_ptr, uint64_t* total) {
-    if (!e || !row_ptr || !total || !e->g.ev) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    if (out) HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));  // the rows move the references first
-    HIP_OK(hipStreamSynchronize(e->stream));
-    const uint32_t n = e->n_docs;
-    std::vector<uint32_t> cnt(n);
-    if (n) HIP_OK(hipMemcpy(cnt.data(), e->g.evn, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint64_t> off(n + 1, 0);
-    for (uint32_t d = 0; d < n; d++) off[d + 1] = off[d] + std::min(cnt[d], e->g.evcap);
-    if (off[n] >= (1ull << 32)) return MT_ERR_ARG;
-    for (uint32_t d = 0; d <= n; d++) row_ptr[d] = (uint32_t)off[d];
-    *total = off[n];
-    if (!out) return MT_OK;
-    if (cap < off[n]) return MT_ERR_ARG;
-    if (off[n]) {
-        uint64_t* d_off = nullptr;
-        mt_event* d_out = nullptr;
-        if (hipMalloc(&d_off, (n + 1) * sizeof(uint64_t)) != hipSuccess) return MT_ERR_NOMEM;
-        if (hipMalloc(&d_out, off[n] * sizeof(mt_event)) != hipSuccess) {
-            (void)hipFree(d_off);
-            return MT_ERR_NOMEM;
-        }
-        mt_status st = MT_OK;
-        if (hipMemcpyAsync(d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            mt_launch_events_pack(&e->g, n, d_off, d_out, e->stream) != hipSuccess ||
-            hipMemcpyAsync(out, d_out, off[n] * sizeof(mt_event), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            st = MT_ERR_HIP;
-        (void)hipFree(d_off);
-        (void)hipFree(d_out);
-        if (st) return st;
-    }
-    HIP_OK(hipMemsetAsync(e->g.evn, 0, (size_t)n * sizeof(uint32_t), e->stream));
-    if (e->g.refcur) HIP_OK(hipMemsetAsync(e->g.refcur, 0, (size_t)n * sizeof(uint32_t), e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    return MT_OK;
-}
-
-// ---- local references (include/mtgpu.h; kernels in mt_refs.hip) ---------------------------------
-mt_status mt_refs_enable(mt_engine* e, uint32_t per_doc) {
-    static_assert(sizeof(mt_ref) == 16 && sizeof(mt_ref_add) == 12 && sizeof(mt_ref_pos) == 12, "reference records");
-    if (!e || (per_doc && !e->g.ev) || per_doc > MT_REFS_MAX) return MT_ERR_ARG;  // (the fold stages a table in LDS)
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    refs_free(e);
-    if (!per_doc) return MT_OK;
-    const size_t D = e->cfg.max_docs;
-    if (hipMalloc(&e->g.refs, D * 2 * per_doc * sizeof(mt_ref)) != hipSuccess ||
-        hipMalloc(&e->g.refpos, D * per_doc * sizeof(mt_ref_pos)) != hipSuccess ||
-        hipMalloc(&e->g.refcur, D * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&e->g.refn, D * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&e->g.refq, D * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&e->g.refdrop, D * sizeof(uint32_t)) != hipSuccess) {
-        refs_free(e);
-        return MT_ERR_NOMEM;
-    }
-    e->g.refcap = per_doc;
-    HIP_OK(refs_clear(e));
-    // (rows recorded before now concern no reference: the first fold only moves the cursors past them)
-    HIP_OK(hipStreamSynchronize(e->stream));
-    return MT_OK;
-}
-
-mt_status mt_refs_add(mt_engine* e, const mt_ref_add* in, uint32_t n, uint32_t* handles) {
-    if (!e || !e->g.refs || (n && (!in || !handles))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (in[i].doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    if (n == 0) return MT_OK;
-    e->gen++;
-    std::vector<mt_pos_query> q(n);
-    for (uint32_t i = 0; i < n; i++) q[i] = mt_pos_query{in[i].doc, in[i].pos, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
-    void* buf = nullptr;
-    const size_t ab = (size_t)n * sizeof(mt_ref_add), qb = (size_t)n * sizeof(mt_pos_query),
-                 rb = (size_t)n * sizeof(mt_pos_result), hb = (size_t)n * sizeof(uint32_t);
-    const size_t o_q = (ab + 15) & ~size_t(15), o_r = o_q + qb, o_h = o_r + rb;
-    if (hipMalloc(&buf, o_h + hb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* b8 = static_cast<uint8_t*>(buf);
-    auto* da = reinterpret_cast<mt_ref_add*>(b8);
-    auto* dq = reinterpret_cast<mt_pos_query*>(b8 + o_q);
-    auto* dr = reinterpret_cast<mt_pos_result*>(b8 + o_r);
-    auto* dh = reinterpret_cast<uint32_t*>(b8 + o_h);
-    hipError_t r = hipMemcpyAsync(da, in, ab, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(dq, q.data(), qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_resolve(&e->g, dq, n, e->n_docs, dr, e->stream);
-    if (r == hipSuccess) r = mt_launch_refs_claim(&e->g, da, dr, n, e->n_docs, dh, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(handles, dh, hb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_refs_remove(mt_engine* e, const uint32_t* docs, const uint32_t* handles, uint32_t n) {
-    if (!e || !e->g.refs || (n && (!docs || !handles))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    if (n == 0) return MT_OK;
-    uint32_t* buf = nullptr;
-    const size_t nb = (size_t)n * sizeof(uint32_t);
-    if (hipMalloc(&buf, 2 * nb) != hipSuccess) return MT_ERR_NOMEM;
-    hipError_t r = hipMemcpyAsync(buf, docs, nb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(buf + n, handles, nb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_refs_release(&e->g, buf, buf + n, n, e->n_docs, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_refs_dropped(mt_engine* e, uint32_t* out, uint32_t n_docs) {
-    if (!e || !e->g.refs || !out || n_docs > e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (n_docs) HIP_OK(hipMemcpy(out, e->g.refdrop, (size_t)n_docs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return MT_OK;
-}
-
-mt_status mt_refs_positions_device(mt_engine* e, const uint32_t* d_docs, const uint32_t* d_handles, uint32_t n,
-                                   mt_ref_pos* d_out) {
-    if (!e || !e->g.refs || (n && (!d_docs || !d_handles || !d_out))) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    HIP_OK(mt_launch_refs_positions(&e->g, d_docs, d_handles, n, e->n_docs, d_out, e->stream));
-    return MT_OK;
-}
-
-mt_status mt_refs_positions(mt_engine* e, const uint32_t* docs, const uint32_t* handles, uint32_t n, mt_ref_pos* out) {
-    if (!e || !e->g.refs || (n && (!docs || !handles || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    if (n == 0) return mt_refs_positions_device(e, nullptr, nullptr, 0, nullptr);
-    uint8_t* buf = nullptr;
-    const size_t nb = (size_t)n * sizeof(uint32_t), ob = (size_t)n * sizeof(mt_ref_pos);
-    if (hipMalloc(&buf, 2 * nb + ob) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dd = reinterpret_cast<uint32_t*>(buf);
-    auto* dout = reinterpret_cast<mt_ref_pos*>(buf + 2 * nb);
-    hipError_t r = hipMemcpyAsync(dd, docs, nb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(dd + n, handles, nb, hipMemcpyHostToDevice, e->stream);
-    mt_status st = MT_OK;
-    if (r == hipSuccess) st = mt_refs_positions_device(e, dd, dd + n, n, dout);
-    if (r == hipSuccess && st == MT_OK) r = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r != hipSuccess ? MT_ERR_HIP : st;
-}
-
-// ---- interval collections (include/mtgpu.h; kernels in mt_intervals.hip) -------------------------
-mt_status mt_intervals_enable(mt_engine* e, uint32_t per_doc) {
-    static_assert(sizeof(mt_interval) == 16 && sizeof(mt_interval_add) == 16 && sizeof(mt_interval_query) == 16 &&
-                      sizeof(mt_interval_pos) == 24,
-                  "interval records");
-    if (!e || (per_doc && (!e->g.refs || 2ull * per_doc > e->g.refcap))) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    intervals_free(e);
-    if (!per_doc) return MT_OK;
-    const size_t D = e->cfg.max_docs;
-    if (hipMalloc(&e->g.ivs, D * per_doc * sizeof(mt_interval)) != hipSuccess ||
-        hipMalloc(&e->g.ivn, D * sizeof(uint32_t)) != hipSuccess) {
-        intervals_free(e);
-        return MT_ERR_NOMEM;
-    }
-    e->g.ivcap = per_doc;
-    HIP_OK(mt_launch_intervals_free_docs(&e->g, nullptr, e->cfg.max_docs, e->cfg.max_docs, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    return MT_OK;
-}
-
-mt_status mt_intervals_add(mt_engine* e, const mt_interval_add* in, uint32_t n, uint32_t* handles) {
-    if (!e || !e->g.ivs || (n && (!in || !handles))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (in[i].doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    if (n == 0) return MT_OK;
-    e->gen++;
-    std::vector<mt_pos_query> q(2 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++) {
-        q[2 * i] = mt_pos_query{in[i].doc, in[i].start, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
-        q[2 * i + 1] = mt_pos_query{in[i].doc, in[i].end, MT_POS_LOCAL, 0, MT_POS_CONTAINING};
-    }
-    void* buf = nullptr;
-    const size_t ab = (size_t)n * sizeof(mt_interval_add), qb = 2 * (size_t)n * sizeof(mt_pos_query),
-                 rb = 2 * (size_t)n * sizeof(mt_pos_result), hb = (size_t)n * sizeof(uint32_t);
-    const size_t o_q = ab, o_r = o_q + qb, o_h = o_r + rb;
-    if (hipMalloc(&buf, o_h + hb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* b8 = static_cast<uint8_t*>(buf);
-    auto* da = reinterpret_cast<mt_interval_add*>(b8);
-    auto* dq = reinterpret_cast<mt_pos_query*>(b8 + o_q);
-    auto* dr = reinterpret_cast<mt_pos_result*>(b8 + o_r);
-    auto* dh = reinterpret_cast<uint32_t*>(b8 + o_h);
-    hipError_t r = hipMemcpyAsync(da, in, ab, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(dq, q.data(), qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_resolve(&e->g, dq, 2 * n, e->n_docs, dr, e->stream);
-    if (r == hipSuccess) r = mt_launch_intervals_claim(&e->g, da, dr, n, e->n_docs, dh, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(handles, dh, hb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_intervals_remove(mt_engine* e, const mt_interval_query* q, uint32_t n, uint32_t* removed) {
-    if (!e || !e->g.ivs || (n && (!q || !removed))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    if (n == 0) return MT_OK;
-    uint8_t* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_interval_query), hb = (size_t)n * sizeof(uint32_t);
-    if (hipMalloc(&buf, qb + hb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = reinterpret_cast<mt_interval_query*>(buf);
-    auto* dh = reinterpret_cast<uint32_t*>(buf + qb);
-    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_intervals_release(&e->g, dq, n, e->n_docs, dh, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(removed, dh, hb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_intervals_overlapping_device(mt_engine* e, const mt_interval_query* d_q, uint32_t n,
-                                          const uint32_t* d_row_ptr, uint32_t* d_counts, uint32_t* d_out) {
-    if (!e || !e->g.ivs || (n && (!d_q || !d_counts || (d_row_ptr && !d_out)))) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    HIP_OK(mt_launch_intervals_overlap(&e->g, d_q, n, e->n_docs, d_row_ptr, d_counts, d_out, e->stream));
-    return MT_OK;
-}
-
-mt_status mt_intervals_overlapping(mt_engine* e, const mt_interval_query* q, uint32_t n, uint32_t* row_ptr,
-                                   uint32_t* out, uint64_t cap, uint64_t* total) {
-    if (!e || !e->g.ivs || !row_ptr || !total || (n && !q)) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    row_ptr[0] = 0;
-    *total = 0;
-    if (n == 0) return mt_intervals_overlapping_device(e, nullptr, 0, nullptr, nullptr, nullptr);
-    // the count pass, the rows' prefix sums on the host, then the write pass
-    uint8_t* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_interval_query), cb = ((size_t)n + 1) * sizeof(uint32_t);
-    if (hipMalloc(&buf, qb + 2 * cb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = reinterpret_cast<mt_interval_query*>(buf);
-    auto* dc = reinterpret_cast<uint32_t*>(buf + qb);
-    auto* drp = reinterpret_cast<uint32_t*>(buf + qb + cb);
-    uint32_t* dout = nullptr;
-    mt_status st = MT_OK;
-    do {
-        std::vector<uint32_t> cnt(n);
-        if (hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            (st = mt_intervals_overlapping_device(e, dq, n, nullptr, dc, nullptr)) != MT_OK ||
-            hipMemcpyAsync(cnt.data(), dc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess) {
-            if (st == MT_OK) st = MT_ERR_HIP;
-            break;
-        }
-        uint64_t sum = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            sum += cnt[i];
-            if (sum >= (1ull << 32)) break;
-            row_ptr[i + 1] = (uint32_t)sum;
-        }
-        if (sum >= (1ull << 32)) {
-            st = MT_ERR_ARG;
-            break;
-        }
-        *total = sum;
-        if (!out || sum == 0) break;
-        if (cap < sum) {
-            st = MT_ERR_ARG;
-            break;
-        }
-        if (hipMalloc(&dout, sum * sizeof(uint32_t)) != hipSuccess) {
-            st = MT_ERR_NOMEM;
-            break;
-        }
-        if (hipMemcpyAsync(drp, row_ptr, cb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            (st = mt_intervals_overlapping_device(e, dq, n, drp, dc, dout)) != MT_OK ||
-            hipMemcpyAsync(out, dout, sum * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess) {
-            if (st == MT_OK) st = MT_ERR_HIP;
-        }
-    } while (0);
-    if (dout) (void)hipFree(dout);
-    (void)hipFree(buf);
-    return st;
-}
-
-mt_status mt_text_ranges_device(mt_engine* e, const mt_text_query* d_q, uint32_t n, const uint32_t* d_row_ptr,
-                                uint16_t* d_units, const uint32_t* d_m_row_ptr, mt_text_marker* d_markers,
-                                mt_text_count* d_counts) {
-    static_assert(sizeof(mt_text_query) == 32 && sizeof(mt_text_marker) == 8 && sizeof(mt_text_count) == 8,
-                  "mt_text_query is 32 bytes, mt_text_marker and mt_text_count 8");
-    if (!e || (n && (!d_q || !d_counts || (d_row_ptr && !d_units) || (d_m_row_ptr && (!d_row_ptr || !d_markers)))))
-        return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_text_ranges(&e->g, d_q, n, e->n_docs, d_row_ptr, d_units, d_m_row_ptr, d_markers, d_counts, e->stream));
-    return MT_OK;
-}
-
-mt_status mt_text_lengths(mt_engine* e, const mt_text_query* q, uint32_t n, mt_text_count* out) {
-    if (!e || (n && (!q || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    uint8_t* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_text_query), cb = (size_t)n * sizeof(mt_text_count);
-    if (hipMalloc(&buf, qb + cb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = reinterpret_cast<mt_text_query*>(buf);
-    auto* dc = reinterpret_cast<mt_text_count*>(buf + qb);
-    hipError_t r = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_text_ranges(&e->g, dq, n, e->n_docs, nullptr, nullptr, nullptr, nullptr, dc, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, dc, cb, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_text_ranges(mt_engine* e, const mt_text_query* q, uint32_t n, uint32_t* row_ptr, uint16_t* units,
-                         uint64_t cap, uint32_t* m_row_ptr, mt_text_marker* markers, uint64_t m_cap, uint64_t* totals) {
-    if (!e || !row_ptr || !m_row_ptr || !totals || (n && !q)) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (q[i].doc >= e->n_docs) return MT_ERR_ARG;
-    row_ptr[0] = m_row_ptr[0] = 0;
-    totals[0] = totals[1] = 0;
-    if (n == 0) return MT_OK;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    // the count pass, the rows' prefix sums on the host, then the write pass
-    uint8_t* buf = nullptr;
-    const size_t qb = (size_t)n * sizeof(mt_text_query), cb = (size_t)n * sizeof(mt_text_count);
-    const size_t rb = (((size_t)n + 1) * sizeof(uint32_t) + 15) & ~size_t(15);
-    if (hipMalloc(&buf, qb + cb + 2 * rb) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dq = reinterpret_cast<mt_text_query*>(buf);
-    auto* dc = reinterpret_cast<mt_text_count*>(buf + qb);
-    auto* drp = reinterpret_cast<uint32_t*>(buf + qb + cb);
-    auto* dmrp = reinterpret_cast<uint32_t*>(buf + qb + cb + rb);
-    uint8_t* dout = nullptr;
-    mt_status st = MT_OK;
-    do {
-        std::vector<mt_text_count> cnt(n);
-        if (hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            (st = mt_text_ranges_device(e, dq, n, nullptr, nullptr, nullptr, nullptr, dc)) != MT_OK ||
-            hipMemcpyAsync(cnt.data(), dc, cb, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess) {
-            if (st == MT_OK) st = MT_ERR_HIP;
-            break;
-        }
-        uint64_t sum = 0, msum = 0;
-        for (uint32_t i = 0; i < n && sum < (1ull << 32) && msum < (1ull << 32); i++) {
-            sum += cnt[i].units;
-            msum += cnt[i].markers;
-            row_ptr[i + 1] = (uint32_t)sum;
-            m_row_ptr[i + 1] = (uint32_t)msum;
-        }
-        if (sum >= (1ull << 32) || msum >= (1ull << 32)) {
-            st = MT_ERR_ARG;
-            break;
-        }
-        totals[0] = sum;
-        totals[1] = msum;
-        if (!units || sum + msum == 0) break;
-        if (cap < sum || m_cap < msum || (msum && !markers)) {
-            st = MT_ERR_ARG;
-            break;
-        }
-        const size_t ub = (sum * sizeof(uint16_t) + 15) & ~size_t(15), mb = msum * sizeof(mt_text_marker);
-        if (hipMalloc(&dout, ub + mb + 16) != hipSuccess) {
-            st = MT_ERR_NOMEM;
-            break;
-        }
-        auto* du = reinterpret_cast<uint16_t*>(dout);
-        auto* dm = reinterpret_cast<mt_text_marker*>(dout + ub);
-        if (hipMemcpyAsync(drp, row_ptr, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(dmrp, m_row_ptr, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            (st = mt_text_ranges_device(e, dq, n, drp, du, dmrp, dm, dc)) != MT_OK ||
-            (sum && hipMemcpyAsync(units, du, sum * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
-            (msum && hipMemcpyAsync(markers, dm, mb, hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
-            hipStreamSynchronize(e->stream) != hipSuccess) {
-            if (st == MT_OK) st = MT_ERR_HIP;
-        }
-    } while (0);
-    if (dout) (void)hipFree(dout);
-    (void)hipFree(buf);
-    return st;
-}
-
-mt_status mt_intervals_positions(mt_engine* e, const uint32_t* docs, uint32_t n, mt_interval_pos* out) {
-    if (!e || !e->g.ivs || (n && (!docs || !out))) return MT_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (docs[i] >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
-    if (n == 0) return MT_OK;
-    uint8_t* buf = nullptr;
-    const size_t db = ((size_t)n * sizeof(uint32_t) + 15) & ~size_t(15), ob = (size_t)n * e->g.ivcap * sizeof(mt_interval_pos);
-    if (hipMalloc(&buf, db + ob) != hipSuccess) return MT_ERR_NOMEM;
-    auto* dd = reinterpret_cast<uint32_t*>(buf);
-    auto* dout = reinterpret_cast<mt_interval_pos*>(buf + db);
-    hipError_t r = hipMemcpyAsync(dd, docs, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = mt_launch_refs_resolve_docs(&e->g, dd, n, e->n_docs, e->stream);
-    if (r == hipSuccess) r = mt_launch_intervals_gather(&e->g, dd, n, e->n_docs, dout, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
+    mt_scratch s;
+    auto [d_ids, d_rp, d_mn, d_cs, d_sg, d_tx] =
+        s.carve<uint32_t, uint32_t, int32_t, int32_t, mt_load_seg, uint8_t>(n, rp.size(), n, n, n_segs, text_bytes);
+    return mt_chain(e->stream, s.status())
+        .h2d(d_ids, doc_ids, n * sizeof(uint32_t))
+        .h2d(d_rp, rp.data(), rp.size() * sizeof(uint32_t))
+        .h2d(d_mn, min_seq, n * sizeof(int32_t))
+        .h2d(d_cs, cur_seq, n * sizeof(int32_t))
+        .h2d(d_sg, n_segs ? segs + seg_row_ptr[0] : nullptr, n_segs * sizeof(mt_load_seg))
+        .h2d(d_tx, text, text_bytes)
+        .launch(mt_launch_load, &e->g, n, d_ids, d_rp, d_sg, d_tx, d_mn, d_cs, e->stream)
+        .launch(mt_launch_refs_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
+        .launch(mt_launch_intervals_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
+        .sync().status();
 }
 
 mt_status mt_batch_upload(mt_engine* e, const mt_op_rec* ops, uint64_t n_ops, const uint8_t* payload,
@@ -1610,10 +784,6 @@ static mt_status apply_end(mt_engine* e, uint32_t nk) {
     }
     return MT_OK;
 }
-
-extern "C" mt_status mt_deli_ticket_on_stream(mt_deli* dl, int32_t device, hipStream_t st, const mt_raw_msg* d_msgs,
-                                              const uint32_t* d_row_ptr, uint32_t n_docs, mt_ticket* d_out,
-                                              mt_op_rec* d_ops, uint64_t n_ops);
 
 namespace {
 // device slots of mt_submit_ticks: the copy stream runs up to kRing - 1 ticks ahead of the apply (a
@@ -2223,580 +1393,6 @@ mt_status mt_class_kernel_name(mt_engine* e, uint32_t capacity, char* buf, uint6
     const size_t n = std::min<size_t>(cap - 1, strlen(tmp));
     memcpy(buf, tmp, n);
     buf[n] = 0;
-    return MT_OK;
-}
-
-mt_status mt_checksums_device(mt_engine* e, uint64_t* d_out, uint32_t n_docs) {
-    if (!e || !d_out || n_docs > e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    if (!n_docs) return MT_OK;
-    HIP_OK(mt_launch_checksum(&e->g, n_docs, d_out, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    return MT_OK;
-}
-
-mt_status mt_checksums(mt_engine* e, uint64_t* out, uint32_t n_docs) {
-    if (!e || !out || n_docs > e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    uint64_t* d = nullptr;
-    HIP_OK(hipMalloc(&d, std::max<uint32_t>(1, n_docs) * sizeof(uint64_t)));
-    hipError_t r = mt_launch_checksum(&e->g, n_docs, d, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(out, d, n_docs * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    hipFree(d);
-    return r == hipSuccess ? MT_OK : MT_ERR_HIP;
-}
-
-mt_status mt_seg_counts(mt_engine* e, uint32_t* out, uint32_t n_docs) {
-    if (!e || !out || n_docs > e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    std::vector<mt_doc_scalars> sc(n_docs);
-    HIP_OK(hipMemcpyAsync(sc.data(), e->g.sc, n_docs * sizeof(mt_doc_scalars), hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    for (uint32_t d = 0; d < n_docs; d++) out[d] = (uint32_t)sc[d].nseg;
-    return MT_OK;
-}
-
-mt_status mt_doc_error(mt_engine* e, uint32_t doc, int32_t* code, int32_t* seq) {
-    if (!e || doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    mt_doc_scalars sc;
-    HIP_OK(hipMemcpyAsync(&sc, e->g.sc + doc, sizeof sc, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (code) *code = sc.err;
-    if (seq) *seq = sc.err_seq;
-    return MT_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------- canonical readout
-namespace {
-// A document's state on the host, narrow or wide (mt_state.h): text as UTF-16 code units, props as
-// a value id per key, overlap as a sorted client list
-struct HostDoc {
-    mt_doc_scalars sc;
-    bool wide = false;
-    std::vector<int32_t> seq, rseq;
-    std::vector<uint32_t> len, toff;
-    std::vector<uint64_t> ovl, props, ovx, ph, pxl, pxh, pxx;
-    std::vector<uint8_t> client, rclient, flags;
-    std::vector<uint16_t> chi;                 // (wide) the short ids' high bytes
-    std::vector<uint16_t> text;                // the arena's current half, in code units
-    std::vector<std::vector<uint8_t>> levels;  // per level child counts (level 0 = leaf blocks)
-    uint32_t prop(int i, int k) const {
-        const int sh = 8 * (k & 7);
-        if (!wide) return k < 8 ? (uint32_t)((props[i] >> sh) & 0xFF) : 0u;
-        if (k >= 16 && !(sc.wide & MT_WIDE_XKV)) return 0u;  // (no keys 16..31 stored)
-        const uint64_t lo = k < 8 ? props[i] : k < 16 ? pxl[i] : pxx[4 * (size_t)i + 2 * ((k - 16) >> 3)];
-        const uint64_t hi = k < 8 ? ph[i] : k < 16 ? pxh[i] : pxx[4 * (size_t)i + 2 * ((k - 16) >> 3) + 1];
-        return (uint32_t)((lo >> sh) & 0xFF) | ((uint32_t)((hi >> sh) & 0xFF) << 8);
-    }
-    std::vector<int> overlap(int i) const {
-        std::vector<int> v;
-        for (int c = 0; c < 64; c++)
-            if ((ovl[i] >> c) & 1) v.push_back(c);
-        if (wide) {
-            const uint64_t* x = ovx.data() + (size_t)MT_OVX_WORDS * i;
-            for (int q = 0; q < MT_OVX_IDS; q++) {
-                const int c = (int)mt_ovx_id2(x, (sc.wide & MT_WIDE_XOV) ? x + 4 : nullptr, q);
-                if (!c) break;
-                v.push_back(c);
-            }
-        }
-        return v;
-    }
-    uint32_t client_of(int i) const { return client[i] | (wide ? (uint32_t)(chi[i] & 0xFF) << 8 : 0u); }
-    uint32_t rclient_of(int i) const { return rclient[i] | (wide ? (uint32_t)(chi[i] >> 8) << 8 : 0u); }
-    const uint16_t* units(int i) const { return text.data() + toff[i]; }
-};
-
-template <class T>
-hipError_t fetch(std::vector<T>& v, const T* base, size_t off, size_t n, hipStream_t st) {
-    v.resize(n);
-    if (!n) return hipSuccess;
-    return hipMemcpyAsync(v.data(), base + off, n * sizeof(T), hipMemcpyDeviceToHost, st);
-}
-
-// the current arena half of document d as code units (a narrow document's bytes widened)
-mt_status fetch_text(mt_engine* e, uint32_t d, const mt_doc_scalars& sc, std::vector<uint16_t>& out) {
-    const mt_gstate& g = e->g;
-    const size_t base = ((size_t)d * 2 + sc.text_half) * g.textcap;
-    if (sc.wide & MT_WIDE_DOC) {
-        out.resize(sc.text_top);
-        if (sc.text_top)
-            HIP_OK(hipMemcpyAsync(out.data(), g.text + base, (size_t)sc.text_top * 2, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        return MT_OK;
-    }
-    std::vector<uint8_t> b;
-    HIP_OK(fetch(b, g.text, base, sc.text_top, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    out.assign(b.begin(), b.end());
-    return MT_OK;
-}
-
-mt_status read_doc(mt_engine* e, uint32_t d, HostDoc& h) {
-    const mt_gstate& g = e->g;
-    HIP_OK(hipMemcpyAsync(&h.sc, g.sc + d, sizeof h.sc, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    h.wide = (h.sc.wide & MT_WIDE_DOC) != 0 && g.ovx;
-    const size_t so = (size_t)d * g.segcap, n = (size_t)h.sc.nseg;
-    HIP_OK(fetch(h.seq, g.seq, so, n, e->stream));
-    HIP_OK(fetch(h.rseq, g.rseq, so, n, e->stream));
-    HIP_OK(fetch(h.len, g.len, so, n, e->stream));
-    HIP_OK(fetch(h.toff, g.toff, so, n, e->stream));
-    HIP_OK(fetch(h.ovl, g.ovl, so, n, e->stream));
-    HIP_OK(fetch(h.props, g.props, so, n, e->stream));
-    if (h.wide) {
-        HIP_OK(fetch(h.ovx, g.ovx, so * MT_OVX_WORDS, n * MT_OVX_WORDS, e->stream));
-        HIP_OK(fetch(h.chi, g.chi, so, n, e->stream));
-        HIP_OK(fetch(h.ph, g.ph, so, n, e->stream));
-        HIP_OK(fetch(h.pxl, g.pxl, so, n, e->stream));
-        HIP_OK(fetch(h.pxh, g.pxh, so, n, e->stream));
-        HIP_OK(fetch(h.pxx, g.pxx, so * 4, n * 4, e->stream));
-    }
-    HIP_OK(fetch(h.client, g.client, so, n, e->stream));
-    HIP_OK(fetch(h.rclient, g.rclient, so, n, e->stream));
-    HIP_OK(fetch(h.flags, g.flags, so, n, e->stream));
-    h.levels.resize(h.sc.nlev);
-    for (int L = 0; L < h.sc.nlev; L++) {
-        if (L == 0) HIP_OK(fetch(h.levels[0], g.lbcnt, (size_t)d * g.lbcap, h.sc.nb[0], e->stream));
-        else HIP_OK(fetch(h.levels[L], g.ibcnt, ((size_t)d * (MT_MAXLEV - 1) + (L - 1)) * g.ibcap, h.sc.nb[L], e->stream));
-    }
-    HIP_OK(hipStreamSynchronize(e->stream));
-    return fetch_text(e, d, h.sc, h.text);
-}
-
-// A JSON string of UTF-16 code units, ASCII only: printable ASCII as itself, \" \\ and the short
-// forms JSON.stringify uses (ECMA-262 QuoteJSONString), every other unit -- non-ASCII and surrogate
-// halves included -- as \uXXXX.  It parses to the same string the reference's JSON holds.
-void json_units(std::string& o, const uint16_t* p, size_t n) {
-    o += '"';
-    for (size_t i = 0; i < n; i++) {
-        const unsigned c = p[i];
-        switch (c) {
-            case '"': o += "\\\""; break;
-            case '\\': o += "\\\\"; break;
-            case '\b': o += "\\b"; break;
-            case '\t': o += "\\t"; break;
-            case '\n': o += "\\n"; break;
-            case '\f': o += "\\f"; break;
-            case '\r': o += "\\r"; break;
-            default:
-                if (c < 0x20 || c >= 0x7F) {
-                    char buf[8];
-                    snprintf(buf, sizeof buf, "\\u%04x", c);
-                    o += buf;
-                } else {
-                    o += (char)c;
-                }
-        }
-    }
-    o += '"';
-}
-
-std::string state_json(const HostDoc& h) {
-    std::string o = "{\"seq\":" + std::to_string(h.sc.cur_seq) + ",\"msn\":" + std::to_string(h.sc.min_seq) + ",\"segs\":[";
-    for (int i = 0; i < h.sc.nseg; i++) {
-        if (i) o += ',';
-        o += '[';
-        if (h.flags[i] & MT_SF_MARKER)  // a Marker: {"marker": refType}
-            o += "{\"marker\":" + std::to_string(h.units(i)[0]) + "}";
-        else
-            json_units(o, h.units(i), h.len[i]);
-        const bool rm = h.flags[i] & MT_SF_REMOVED;
-        o += ',' + std::to_string(h.seq[i]) + ',' + std::to_string(mt_canon_client(h.client_of(i))) + ',';
-        o += (rm ? std::to_string(h.rseq[i]) : "-1") + ',' + (rm ? std::to_string(h.rclient_of(i)) : "-1") + ",[";
-        bool f = true;
-        for (int c : h.overlap(i)) {
-            if (!f) o += ',';
-            f = false;
-            o += std::to_string(c);
-        }
-        o += "],";
-        if (!(h.flags[i] & MT_SF_PDEF)) {
-            o += "null";
-        } else {
-            o += '{';
-            bool f2 = true;
-            for (int k = 0; k < MT_MAX_KEYS_WIDE; k++) {
-                const unsigned v = h.prop(i, k);
-                if (!v) continue;
-                if (!f2) o += ',';
-                f2 = false;
-                o += "\"k" + std::to_string(k) + "\":" + std::to_string(v);
-            }
-            o += '}';
-        }
-        o += ']';
-    }
-    o += "],\"tree\":[";
-    for (int depth = 0; depth < h.sc.nlev; depth++) {
-        const auto& lv = h.levels[h.sc.nlev - 1 - depth];
-        if (depth) o += ',';
-        o += '[';
-        for (size_t b = 0; b < lv.size(); b++) {
-            if (b) o += ',';
-            o += std::to_string(lv[b]);
-        }
-        o += ']';
-    }
-    o += "]}";
-    return o;
-}
-
-// props as the reference's map: keys "k<id>" (interned key ids), values = interned value ids
-void props_json(std::string& o, const HostDoc& h, int i) {
-    o += '{';
-    bool first = true;
-    for (int k = 0; k < MT_MAX_KEYS_WIDE; k++) {
-        const unsigned v = h.prop(i, k);
-        if (!v) continue;
-        if (!first) o += ',';
-        first = false;
-        o += "\"k" + std::to_string(k) + "\":" + std::to_string(v);
-    }
-    o += '}';
-}
-
-// TextSegment.toJSONObject (textSegment.ts:47-53) of `text` with the props of segment i;
-// Marker.toJSONObject (mergeTree.ts:652-656) for a marker: {marker: {refType}, props?}
-void seg_json(std::string& o, const HostDoc& h, int i, const std::vector<uint16_t>& text) {
-    if (h.flags[i] & MT_SF_MARKER) {
-        o += "{\"marker\":{\"refType\":" + std::to_string(h.units(i)[0]) + "}";
-        if (h.flags[i] & MT_SF_PDEF) {
-            o += ",\"props\":";
-            props_json(o, h, i);
-        }
-        o += '}';
-    } else if (h.flags[i] & MT_SF_PDEF) {
-        o += "{\"text\":";
-        json_units(o, text.data(), text.size());
-        o += ",\"props\":";
-        props_json(o, h, i);
-        o += '}';
-    } else {
-        json_units(o, text.data(), text.size());
-    }
-}
-
-std::string client_name(const char* const* names, uint32_t n_names, uint32_t c) {
-    if (c == MT_CLIENT_NONCOLLAB) return "original";  // Client.getLongClientId of a negative id (client.ts:645-652)
-    if (names && c < n_names && names[c]) return names[c];
-    return std::to_string(c);
-}
-
-// SnapshotV1.emit (snapshotV1.ts:85-149) from the device's extraction specs: the tree entries as
-// one JSON object {"header": chunk, "body_0": chunk, ...}
-std::string snapshot_json(const HostDoc& h, const std::vector<uint32_t>& sp, uint32_t nspec, uint32_t chunk,
-                          const char* const* names, uint32_t n_names) {
-    std::vector<std::string> specs(nspec);
-    std::vector<uint32_t> lens(nspec);
-    for (uint32_t k = 0; k < nspec; k++) {
-        const int pos = (int)sp[3 * k];
-        const int cnt = (int)(sp[3 * k + 1] >> 1);
-        const bool meta = sp[3 * k + 1] & 1u;
-        std::vector<uint16_t> text;
-        for (int i = pos; i < pos + cnt; i++) {
-            // elided inside the run: removed at or below the MSN, or a pending local insert / removal
-            if (h.seq[i] == -1 || ((h.flags[i] & MT_SF_REMOVED) && h.rseq[i] <= h.sc.min_seq)) continue;
-            text.insert(text.end(), h.units(i), h.units(i) + h.len[i]);
-        }
-        lens[k] = sp[3 * k + 2];
-        std::string& o = specs[k];
-        if (!meta) {
-            seg_json(o, h, pos, text);
-            continue;
-        }
-        o += "{\"json\":";
-        seg_json(o, h, pos, text);
-        if (h.seq[pos] > h.sc.min_seq)
-            o += ",\"seq\":" + std::to_string(h.seq[pos]) + ",\"client\":\"" + client_name(names, n_names, h.client_of(pos)) +
-                 "\"";
-        if (h.flags[pos] & MT_SF_REMOVED)
-            o += ",\"removedSeq\":" + std::to_string(h.rseq[pos]) + ",\"removedClient\":\"" +
-                 client_name(names, n_names, h.rclient_of(pos)) + "\"";
-        o += '}';
-    }
-    // getSeqLengthSegs (:57-79): chunks of >= `chunk` characters
-    struct Chunk { uint32_t start, count; uint64_t length; };
-    std::vector<Chunk> chunks;
-    uint32_t total_count = 0;
-    uint64_t total_len = 0;
-    do {
-        Chunk c{total_count, 0, 0};
-        while (c.length < chunk && c.start + c.count < nspec) c.length += lens[c.start + c.count++];
-        chunks.push_back(c);
-        total_count += c.count;
-        total_len += c.length;
-    } while (total_count < nspec);
-    auto chunk_json = [&](const Chunk& c, bool header) {
-        std::string o = "{\"version\":\"1\",\"segmentCount\":" + std::to_string(c.count) + ",\"length\":" +
-                        std::to_string(c.length) + ",\"segments\":[";
-        for (uint32_t k = 0; k < c.count; k++) {
-            if (k) o += ',';
-            o += specs[c.start + k];
-        }
-        o += "],\"startIndex\":" + std::to_string(c.start);
-        if (header) {
-            o += ",\"headerMetadata\":{\"minSequenceNumber\":" + std::to_string(h.sc.min_seq) +
-                 ",\"sequenceNumber\":" + std::to_string(h.sc.cur_seq) + ",\"orderedChunkMetadata\":[{\"id\":\"header\"}";
-            for (size_t b = 1; b < chunks.size(); b++) o += ",{\"id\":\"body_" + std::to_string(b - 1) + "\"}";
-            o += "],\"totalLength\":" + std::to_string(total_len) + ",\"totalSegmentCount\":" +
-                 std::to_string(total_count) + '}';
-        }
-        return o + '}';
-    };
-    std::string o = "{\"header\":" + chunk_json(chunks[0], true);
-    for (size_t b = 1; b < chunks.size(); b++) o += ",\"body_" + std::to_string(b - 1) + "\":" + chunk_json(chunks[b], false);
-    return o + '}';
-}
-
-// Documents [d0, d0 + n) to the host in one pass: every field of the range in one copy each, the
-// text arenas per document, all asynchronous behind one synchronisation
-mt_status read_range(mt_engine* e, uint32_t d0, uint32_t n, std::vector<HostDoc>& out) {
-    const mt_gstate& g = e->g;
-    std::vector<mt_doc_scalars> sc(n);
-    HIP_OK(hipMemcpyAsync(sc.data(), g.sc + d0, n * sizeof(mt_doc_scalars), hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-    const size_t S = (size_t)n * g.segcap, so = (size_t)d0 * g.segcap;
-    std::vector<int32_t> seq, rseq;
-    std::vector<uint32_t> len, toff;
-    std::vector<uint64_t> ovl, props, ovx, ph, pxl, pxh, pxx;
-    std::vector<uint8_t> client, rclient, flags, lb, ib;
-    std::vector<uint16_t> chi;
-    bool any_wide = false;
-    for (uint32_t i = 0; i < n; i++) any_wide = any_wide || ((sc[i].wide & MT_WIDE_DOC) && g.ovx);
-    HIP_OK(fetch(seq, g.seq, so, S, e->stream));
-    HIP_OK(fetch(rseq, g.rseq, so, S, e->stream));
-    HIP_OK(fetch(len, g.len, so, S, e->stream));
-    HIP_OK(fetch(toff, g.toff, so, S, e->stream));
-    HIP_OK(fetch(ovl, g.ovl, so, S, e->stream));
-    HIP_OK(fetch(props, g.props, so, S, e->stream));
-    if (any_wide) {
-        HIP_OK(fetch(ovx, g.ovx, so * MT_OVX_WORDS, S * MT_OVX_WORDS, e->stream));
-        HIP_OK(fetch(chi, g.chi, so, S, e->stream));
-        HIP_OK(fetch(ph, g.ph, so, S, e->stream));
-        HIP_OK(fetch(pxl, g.pxl, so, S, e->stream));
-        HIP_OK(fetch(pxh, g.pxh, so, S, e->stream));
-        HIP_OK(fetch(pxx, g.pxx, so * 4, S * 4, e->stream));
-    }
-    HIP_OK(fetch(client, g.client, so, S, e->stream));
-    HIP_OK(fetch(rclient, g.rclient, so, S, e->stream));
-    HIP_OK(fetch(flags, g.flags, so, S, e->stream));
-    HIP_OK(fetch(lb, g.lbcnt, (size_t)d0 * g.lbcap, (size_t)n * g.lbcap, e->stream));
-    HIP_OK(fetch(ib, g.ibcnt, (size_t)d0 * (MT_MAXLEV - 1) * g.ibcap, (size_t)n * (MT_MAXLEV - 1) * g.ibcap, e->stream));
-    out.assign(n, HostDoc());
-    HIP_OK(hipStreamSynchronize(e->stream));
-    for (uint32_t i = 0; i < n; i++) {
-        HostDoc& h = out[i];
-        h.sc = sc[i];
-        h.wide = (sc[i].wide & MT_WIDE_DOC) && g.ovx;
-        mt_status st = fetch_text(e, d0 + i, sc[i], h.text);
-        if (st) return st;
-        const size_t a = (size_t)i * g.segcap, m = (size_t)h.sc.nseg;
-        h.seq.assign(seq.begin() + a, seq.begin() + a + m);
-        h.rseq.assign(rseq.begin() + a, rseq.begin() + a + m);
-        h.len.assign(len.begin() + a, len.begin() + a + m);
-        h.toff.assign(toff.begin() + a, toff.begin() + a + m);
-        h.ovl.assign(ovl.begin() + a, ovl.begin() + a + m);
-        h.props.assign(props.begin() + a, props.begin() + a + m);
-        if (h.wide) {
-            h.ovx.assign(ovx.begin() + a * MT_OVX_WORDS, ovx.begin() + (a + m) * MT_OVX_WORDS);
-            h.chi.assign(chi.begin() + a, chi.begin() + a + m);
-            h.ph.assign(ph.begin() + a, ph.begin() + a + m);
-            h.pxl.assign(pxl.begin() + a, pxl.begin() + a + m);
-            h.pxh.assign(pxh.begin() + a, pxh.begin() + a + m);
-            h.pxx.assign(pxx.begin() + a * 4, pxx.begin() + (a + m) * 4);
-        }
-        h.client.assign(client.begin() + a, client.begin() + a + m);
-        h.rclient.assign(rclient.begin() + a, rclient.begin() + a + m);
-        h.flags.assign(flags.begin() + a, flags.begin() + a + m);
-        h.levels.resize(h.sc.nlev);
-        for (int L = 0; L < h.sc.nlev; L++) {
-            const uint8_t* src = L == 0 ? lb.data() + (size_t)i * g.lbcap
-                                        : ib.data() + ((size_t)i * (MT_MAXLEV - 1) + (L - 1)) * g.ibcap;
-            h.levels[L].assign(src, src + h.sc.nb[L]);
-        }
-    }
-    return MT_OK;
-}
-
-mt_status copy_out(const std::string& s, char* buf, uint64_t cap, uint64_t* len) {
-    if (len) *len = s.size();
-    if (buf && cap) {
-        const uint64_t n = std::min<uint64_t>(cap - 1, s.size());
-        memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return MT_OK;
-}
-}  // namespace
-
-extern "C" {
-
-mt_status mt_get_state(mt_engine* e, uint32_t doc, char* buf, uint64_t cap, uint64_t* len) {
-    if (!e || doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HostDoc h;
-    mt_status st = read_doc(e, doc, h);
-    if (st) return st;
-    return copy_out(state_json(h), buf, cap, len);
-}
-
-mt_status mt_get_snapshot(mt_engine* e, uint32_t doc, uint32_t chunk_size, const char* const* client_names,
-                          uint32_t n_names, char* buf, uint64_t cap, uint64_t* len) {
-    if (!e || doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HostDoc h;
-    mt_status st = read_doc(e, doc, h);
-    if (st) return st;
-    const uint32_t scap = std::max<uint32_t>(1, (uint32_t)h.sc.nseg);
-    uint32_t* d = nullptr;
-    HIP_OK(hipMalloc(&d, (3 * (size_t)scap + 1) * sizeof(uint32_t)));
-    std::vector<uint32_t> sp(3 * (size_t)scap);
-    uint32_t nspec = 0;
-    hipError_t r = mt_launch_snapshot(&e->g, doc, 1, scap, d + 1, d, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(&nspec, d, sizeof nspec, hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(sp.data(), d + 1, sp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(d);
-    if (r != hipSuccess) return MT_ERR_HIP;
-    if (nspec > scap) return MT_ERR_STATE;
-    return copy_out(snapshot_json(h, sp, nspec, chunk_size ? chunk_size : 10000u, client_names, n_names), buf, cap,
-                    len);
-}
-
-mt_status mt_get_snapshots(mt_engine* e, uint32_t d0, uint32_t n, uint32_t chunk_size, const char* const* client_names,
-                           uint32_t n_names, char* buf, uint64_t cap, uint64_t* offsets) {
-    if (!e || !offsets || d0 > e->n_docs || n > e->n_docs - d0) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    // a sizing call (buf NULL) leaves its result for the copying call with the same arguments
-    auto& c = e->snap_cache;
-    const bool hit = c.valid && c.gen == e->gen && c.d0 == d0 && c.n == n && c.chunk == chunk_size && c.names == client_names &&
-                     c.n_names == n_names;
-    if (!hit) {
-        c.valid = false;
-        c.json.clear();
-        c.off.assign(n + 1, 0);
-        if (n) {
-            std::vector<HostDoc> docs;
-            mt_status st = read_range(e, d0, n, docs);
-            if (st) return st;
-            // the device extraction of every document in one launch
-            const uint32_t scap = e->g.segcap;
-            uint32_t *specs = nullptr, *counts = nullptr;
-            if (hipMalloc(&specs, (size_t)n * scap * 3 * sizeof(uint32_t)) != hipSuccess) return MT_ERR_NOMEM;
-            if (hipMalloc(&counts, (size_t)n * sizeof(uint32_t)) != hipSuccess) {
-                (void)hipFree(specs);
-                return MT_ERR_NOMEM;
-            }
-            std::vector<uint32_t> hc(n), hs((size_t)n * scap * 3);
-            hipError_t r = mt_launch_snapshot(&e->g, d0, n, scap, specs, counts, e->stream);
-            if (r == hipSuccess) r = hipMemcpyAsync(hc.data(), counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-            if (r == hipSuccess) r = hipMemcpyAsync(hs.data(), specs, hs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-            if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-            (void)hipFree(specs);
-            (void)hipFree(counts);
-            if (r != hipSuccess) return MT_ERR_HIP;
-            // the JSON of each document on the host cores, in parallel
-            std::vector<std::string> parts(n);
-            std::atomic<uint32_t> next{0};
-            std::atomic<int> bad{0};
-            const unsigned nt = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), std::min(16u, n));
-            auto work = [&] {
-                for (uint32_t i; (i = next.fetch_add(1)) < n;) {
-                    if (hc[i] > scap) {
-                        bad = 1;
-                        continue;
-                    }
-                    std::vector<uint32_t> sp(hs.begin() + (size_t)i * scap * 3, hs.begin() + ((size_t)i * scap + hc[i]) * 3);
-                    parts[i] = snapshot_json(docs[i], sp, hc[i], chunk_size ? chunk_size : 10000u, client_names, n_names);
-                }
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-            work();
-            for (auto& x : th) x.join();
-            if (bad) return MT_ERR_STATE;
-            for (uint32_t i = 0; i < n; i++) c.off[i + 1] = c.off[i] + parts[i].size();
-            c.json.reserve(c.off[n]);
-            for (auto& p : parts) c.json += p;
-        }
-        c.valid = true;
-        c.gen = e->gen;
-        c.d0 = d0;
-        c.n = n;
-        c.chunk = chunk_size;
-        c.names = client_names;
-        c.n_names = n_names;
-    }
-    for (uint32_t i = 0; i <= n; i++) offsets[i] = c.off[i];
-    if (!buf) return MT_OK;
-    if (cap < c.json.size()) return MT_ERR_ARG;
-    memcpy(buf, c.json.data(), c.json.size());
-    c.valid = false;  // consumed
-    c.json.clear();
-    c.json.shrink_to_fit();
-    return MT_OK;
-}
-
-mt_status mt_snapshot_extract(mt_engine* e, uint32_t d0, uint32_t n, float* kernel_ms, uint64_t* n_specs) {
-    if (!e || d0 > e->n_docs || n > e->n_docs - d0) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    if (n == 0) return MT_OK;
-    const uint32_t cap = e->g.segcap;
-    uint32_t *specs = nullptr, *counts = nullptr;
-    if (hipMalloc(&specs, (size_t)n * cap * 3 * sizeof(uint32_t)) != hipSuccess) return MT_ERR_NOMEM;
-    if (hipMalloc(&counts, (size_t)n * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipFree(specs);
-        return MT_ERR_NOMEM;
-    }
-    hipError_t r = hipEventRecord(e->ev0, e->stream);
-    if (r == hipSuccess) r = mt_launch_snapshot(&e->g, d0, n, cap, specs, counts, e->stream);
-    if (r == hipSuccess) r = hipEventRecord(e->ev1, e->stream);
-    if (r == hipSuccess) r = hipEventSynchronize(e->ev1);
-    float ms = 0.f;
-    if (r == hipSuccess) r = hipEventElapsedTime(&ms, e->ev0, e->ev1);
-    std::vector<uint32_t> hc(n);
-    if (r == hipSuccess) r = hipMemcpy(hc.data(), counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(specs);
-    (void)hipFree(counts);
-    if (r != hipSuccess) return MT_ERR_HIP;
-    uint64_t tot = 0;
-    for (uint32_t c : hc) tot += c;
-    if (kernel_ms) *kernel_ms = ms;
-    if (n_specs) *n_specs = tot;
-    return MT_OK;
-}
-
-mt_status mt_get_text(mt_engine* e, uint32_t doc, char* buf, uint64_t cap, uint64_t* len) {
-    if (!e || doc >= e->n_docs) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HostDoc h;
-    mt_status st = read_doc(e, doc, h);
-    if (st) return st;
-    std::string t;  // UTF-16 code units, little endian
-    for (int i = 0; i < h.sc.nseg; i++)
-        if (!(h.flags[i] & (MT_SF_REMOVED | MT_SF_MARKER)))  // gatherText: text segments only
-            for (uint32_t q = 0; q < h.len[i]; q++) {
-                t += (char)(h.units(i)[q] & 0xFF);
-                t += (char)(h.units(i)[q] >> 8);
-            }
-    return copy_out(t, buf, cap, len);
-}
-
-mt_status mt_get_length(mt_engine* e, uint32_t doc, uint32_t* len) {
-    if (!e || doc >= e->n_docs || !len) return MT_ERR_ARG;
-    HIP_OK(hipSetDevice(e->cfg.device));
-    HostDoc h;
-    mt_status st = read_doc(e, doc, h);
-    if (st) return st;
-    uint32_t n = 0;
-    for (int i = 0; i < h.sc.nseg; i++)
-        if (!(h.flags[i] & MT_SF_REMOVED)) n += h.len[i];
-    *len = n;
     return MT_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/mtgpu.h"
+#include "mt_launch.h"
 #include "mt_state.h"
 #include "mt_wave.h"
 

@@ -10,5 +10,6 @@ mkdir -p ablib
   -Wno-unused-value $FLAGS -c fluidframework_amd/csrc/mt_apply.hip -o ablib/${NAME}_apply.o
 B=fluidframework_amd/build
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ablib/libmtgpu_${NAME}.so ablib/${NAME}_apply.o $B/mt_apply_reg.hip.o \
-  $B/mt_service.hip.o $B/mt_deli.hip.o $B/mt_engine.cpp.o $B/mt_comm.cpp.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+  $B/mt_service.hip.o $B/mt_refs.hip.o $B/mt_intervals.hip.o $B/mt_text.hip.o $B/mt_deli.hip.o $B/mt_engine.cpp.o \
+  $B/mt_queries.cpp.o $B/mt_readout.cpp.o $B/mt_comm.cpp.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo ablib/libmtgpu_${NAME}.so
