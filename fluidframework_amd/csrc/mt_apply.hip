@@ -21,6 +21,7 @@
 #include "../../include/mtgpu.h"
 #include "mt_checksum.h"
 #include "mt_launch.h"
+#include "mt_marker.h"
 #include "mt_state.h"
 #include "mt_synth.h"
 #include "mt_wave.h"
@@ -1687,7 +1688,77 @@ struct Wave {
         if (ev && s.evn > (int)evcap) fail(MT_DERR_EVENTS, S);
     }
 
+    // One relative end (include/mtgpu.h "marker-relative positions") in the view rel_lower scanned
+    // into cum: the marker the block names (mt_marker.h), its exclusive prefix, the end's position.
+    // false: the id names no linked marker.
+    MT_DEV bool rel_resolve(const uint8_t* blk, int32_t* pos) {
+        const mt_rel_end r = mt_rel_decode(blk);
+        const int n = s.n;
+        mt_marker_best best;
+        if (r.value != 0 && r.key < (uint32_t)kKeys) {
+            for (int base = 0; base < n; base += 64) {
+                const int i = base + lane;
+                if (i < n) {
+                    const int sl = s.order[i];
+                    const uint8_t f = s.flags[sl];
+                    best.fold((f & MT_SF_MARKER) && (f & MT_SF_PDEF) && pval(sl, (int)r.key) == r.value, s.seq[sl], i);
+                }
+            }
+        }
+        const int k = mt_marker_pick(best);
+        if (k < 0) return false;
+        *pos = mt_rel_position(cstart(k), s.len[s.order[k]], r.before, r.offset);
+        return true;
+    }
+    // A record with relative ends: getValidOpRange (client.ts:485-502) resolves them in the op's
+    // view, then the op applies as the absolute one would: `o`, a copy of the record, gets the
+    // positions filled in and the blocks cut off its payload's tail, for apply_abs.  false: the
+    // record is refused (the document's error is set).  *unres: a range whose ends both name no
+    // marker, the reference's (-1, -1).
+    MT_DEV bool rel_lower(const mt_op_rec& op, const uint8_t* payload, mt_op_rec& o, bool* unres) {
+        const int32_t S = op.seq;
+        const int type = MT_OP_BASE(op);
+        s.evseq = S;
+        o.type = (uint8_t)(op.type & ~MT_OP_REL);
+        if (S < MT_SEQ_REGEN) return fail(MT_DERR_SEQ_ORDER, S), false;  // a message deli did not send (MT_SEQ_NACK)
+        if (S < 0 || type > MT_OP_ANNOTATE || (type == MT_OP_INSERT && (op.type & MT_OP_REL2)) ||
+            op.payload_len < MT_OP_PAIRS_LEN(op))
+            return fail(MT_DERR_BAD_OP, S), false;
+        o.payload_len = op.payload_len - MT_OP_REL_LEN(op);
+        if constexpr (LOC) {  // the editing client's own message: the ack of the edit its host resolved
+            if (s.lc.own >= 0 && (int)op.client == s.lc.own) return true;
+        }
+        if (MT_OP_IS_NOOP(op)) return true;  // the empty string: dropped (client.ts:403-407)
+        constexpr int kClients = W ? MT_MAX_CLIENTS_WIDE : MT_MAX_CLIENTS;
+        if (((op.type & MT_OP_WIDE) && !W) || op.client == 0 || op.client >= kClients || op.client == MT_CLIENT_NONCOLLAB)
+            return fail(MT_DERR_LIMITS, S), false;
+        scan(op.ref_seq, (int)op.client);
+        const uint8_t* blk = payload + op.payload_off + o.payload_len;
+        int missing = 0, ends = 0;
+        for (int e = 0; e < 2; e++) {
+            if (!(op.type & (e ? MT_OP_REL2 : MT_OP_REL1))) continue;
+            int32_t pos = -1;
+            if (!rel_resolve(blk + MT_REL_BYTES * ends, &pos)) missing++;
+            if (e) o.pos2 = pos;
+            else o.pos1 = pos;
+            ends++;
+        }
+        if (missing == 0) return true;
+        // unresolved: the reference's -1.  A range with both ends so is applied as (-1, -1)
+        if (type == MT_OP_INSERT || missing != 2) return fail(MT_DERR_BAD_OP, S), false;
+        *unres = true;
+        return true;
+    }
+
+    // (one call of apply_abs: the engine's body is inlined once)
     MT_DEV void apply(const mt_op_rec& op, const uint8_t* payload) {
+        mt_op_rec o = op;
+        bool unres = false;
+        if ((op.type & MT_OP_REL) && !rel_lower(op, payload, o, &unres)) return;
+        apply_abs(o, payload, unres);
+    }
+    // unres: a range rel_lower left at (-1, -1); every other negative position is refused
+    MT_DEV void apply_abs(const mt_op_rec& op, const uint8_t* payload, bool unres) {
         const int np = MT_OP_NPAIRS(op);
         const int32_t S = op.seq;
         const int type = MT_OP_TYPE(op);
@@ -1731,7 +1802,7 @@ struct Wave {
         for (int q = 0; q < np; q++)
             if (pr.key(q) >= pr.key_limit() || (W && pr.key(q) >= 16 && !xk_p)) return fail(MT_DERR_LIMITS, S);
         if (!noop) {
-            if (op.pos1 < 0 || (type != MT_OP_INSERT && !load && op.pos2 < 0)) return fail(MT_DERR_BAD_OP, S);
+            if (!unres && (op.pos1 < 0 || (type != MT_OP_INSERT && !load && op.pos2 < 0))) return fail(MT_DERR_BAD_OP, S);
             const int L = scan(op.ref_seq, C);  // cum for the op's view (no edit yet)
             // the window asserts run after the op in the reference (completeAndLogOp, client.ts:461-464;
             // updateSeqNumbers :826), so a failing insert (mergeTree.ts:2210) is reported first; all of

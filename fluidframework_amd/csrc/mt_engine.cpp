@@ -228,7 +228,9 @@ static bool wide_rec(const mt_op_rec& o) {
 }
 // Payload bounds (the kernels trust these) and whether any record needs the wide document form, in
 // one pass; a big batch is checked on all host cores.  Result bit 0: a payload out of bounds, bit 1:
-// wide.
+// wide.  The blocks of a record's marker-relative ends lie inside its payload_len (its tail,
+// MT_OP_PAIRS_LEN), so this bound covers them here and in mt_scan_records_kernel; a record shorter than
+// its tail is the engines' to refuse (MT_DERR_BAD_OP), as one shorter than its pairs is.
 static int scan_records(const mt_op_rec* ops, uint64_t n_ops, uint64_t payload_bytes) {
     auto scan_range = [&](uint64_t lo, uint64_t hi) {
         bool bad = false, wide = false;

@@ -100,6 +100,10 @@ hipError_t mt_launch_text_ranges(const mt_gstate* g, const mt_text_query* q, uin
                                  const uint32_t* row_ptr, uint16_t* units, const uint32_t* m_row_ptr,
                                  mt_text_marker* markers, mt_text_count* counts, hipStream_t st);
 
+// ---- mt_markers.hip: marker ids
+hipError_t mt_launch_marker_positions(const mt_gstate* g, const mt_marker_query* q, uint32_t n, uint32_t n_docs,
+                                      mt_marker_result* out, hipStream_t st);
+
 // ---- mt_deli.hip: the ticket kernel on the apply engine's stream (mt_submit_ticks_deli)
 mt_status mt_deli_ticket_on_stream(mt_deli* dl, int32_t device, hipStream_t st, const mt_raw_msg* d_msgs,
                                    const uint32_t* d_row_ptr, uint32_t n_docs, mt_ticket* d_out, mt_op_rec* d_ops,

@@ -1,5 +1,5 @@
-// mt_queries.cpp -- the query entry points of libmtgpu.so (include/mtgpu.h): tiles, positions,
-// segment infos and text, the regeneration drain, stacks, events, local references, interval
+// mt_queries.cpp -- the query entry points of libmtgpu.so (include/mtgpu.h): tiles, positions, marker
+// ids, segment infos and text, the regeneration drain, stacks, events, local references, interval
 // collections, text reads, checksums, segment counts and the document error.
 //
 // A batched query is one round trip on the engine stream (mt_scratch.h): argument check, the
@@ -51,6 +51,30 @@ mt_status mt_resolve_positions_device(mt_engine* e, const mt_pos_query* d_q, uin
     if (n == 0) return MT_OK;
     HIP_OK(hipSetDevice(e->cfg.device));
     HIP_OK(mt_launch_resolve(&e->g, d_q, n, e->n_docs, d_out, e->stream));
+    return MT_OK;
+}
+
+mt_status mt_marker_positions(mt_engine* e, const mt_marker_query* q, uint32_t n, mt_marker_result* out) {
+    static_assert(sizeof(mt_marker_query) == 16 && sizeof(mt_marker_result) == 16, "mt_marker_query / result are 16 bytes");
+    if (!e || (n && (!q || !out)) || !mt_docs_below(q, n, e->n_docs)) return MT_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].key >= MT_MAX_KEYS_WIDE) return MT_ERR_ARG;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    mt_scratch s;
+    auto [dq, dr] = s.carve<mt_marker_query, mt_marker_result>(n, n);
+    return mt_chain(e->stream, s.status())
+        .h2d(dq, q, n * sizeof *q)
+        .launch(mt_launch_marker_positions, &e->g, dq, n, e->n_docs, dr, e->stream)
+        .d2h(out, dr, n * sizeof *out)
+        .sync().status();
+}
+
+mt_status mt_marker_positions_device(mt_engine* e, const mt_marker_query* d_q, uint32_t n, mt_marker_result* d_out) {
+    if (!e || (n && (!d_q || !d_out))) return MT_ERR_ARG;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    HIP_OK(mt_launch_marker_positions(&e->g, d_q, n, e->n_docs, d_out, e->stream));
     return MT_OK;
 }
 

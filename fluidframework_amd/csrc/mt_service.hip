@@ -242,7 +242,8 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
             const bool wdoc0 = wdoc;
             // snapshot body appends (MT_OP_LOAD, SnapshotLoader.loadBody) are applied by the LDS
             // engine only: the register engine's hot loop stays free of them
-            bool lds_only = false, editing = own >= 0;
+            // a record with marker-relative ends (include/mtgpu.h) is resolved by the LDS engine only
+            bool lds_only = false, editing = own >= 0, rel = false;
             const uint32_t pend = own >= 0 ? g.loc[d].ghi - g.loc[d].glo : 0u;  // pending edits
             uint32_t nloc = 0, nregen = 0;  // (an editing document: its local edits / reconnects here)
             // the wide form's extension (mt_state.h MT_WIDE_XK / MT_WIDE_XO): a property key >= 16 in
@@ -260,7 +261,8 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
             int32_t s_hi = sc.cur_seq, r_lo = 0x7fffffff;
             for (uint32_t i = a; ops && i < b; i++) {
                 const mt_op_rec o = ops[i];
-                const uint32_t ty = MT_OP_TYPE(o);
+                const uint32_t ty = MT_OP_BASE(o);  // (a relative record counts as its base type)
+                rel = rel || (o.type & MT_OP_REL);
                 lds_only = lds_only || ty == MT_OP_LOAD;
                 editing = editing || (o.seq == -1 && o.type != MT_OP_LOAD);
                 nloc += o.seq == -1 ? 1u : 0u;
@@ -271,10 +273,10 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 r_lo = (!MT_OP_IS_NOOP(o) && o.ref_seq < r_lo) ? o.ref_seq : r_lo;
                 if (o.type & MT_OP_WIDE) {
                     const uint32_t np = MT_OP_NPAIRS(o);
-                    if (np && (!payload || o.payload_len < 3u * np)) {
+                    if (np && (!payload || o.payload_len < MT_OP_PAIRS_LEN(o))) {
                         key16 = true;  // (unread pairs: the extension, to be safe)
                     } else {
-                        const uint8_t* pp = payload + o.payload_off + (o.payload_len - 3u * np);
+                        const uint8_t* pp = payload + o.payload_off + (o.payload_len - MT_OP_PAIRS_LEN(o));
                         for (uint32_t q = 0; q < np; q++) key16 = key16 || pp[3 * q] >= 16;
                     }
                 }
@@ -364,7 +366,8 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
             // without the records): the LDS engine, for this launch only
             // (the classes up to 64 * MT_SW_EXACT_K slots keep exact numbers and run any launch)
             // (cls, not c: the wide remap above has left c outside the class table, or at -1)
-            const bool off_win = classes[4 * cls] > 64 * MT_SW_EXACT_K && (!ops || !mt_sw_fits(s_hi, r_lo, sc.min_seq));
+            // A launch with a relative record: the same, at every register class.
+            const bool off_win = rel || (classes[4 * cls] > 64 * MT_SW_EXACT_K && (!ops || !mt_sw_fits(s_hi, r_lo, sc.min_seq)));
             if (!wdoc && c < first_lds && (needs_lds || c64 || off_win)) {
                 // the LDS engine at a register class's capacity, or the register engine's C64 form
                 const int lds_base = n_classes + 1 + (n_classes > first_wide ? n_classes - first_wide : 0);
@@ -425,7 +428,9 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
 // applies the op (mergeTree.ts:2210-2216 throws) before completeAndLogOp's and updateSeqNumbers'
 // asserts (client.ts:461-464, 826).  The halted state is the state before that op, so
 // getLength(refSeq, client) is read from HBM.  One thread per document; the loop runs only for
-// such (rare) documents.
+// such (rare) documents.  An insert at a marker-relative position is left with the recorded error:
+// its position is the LDS engine's to resolve, which has decided the precedence itself (MT_OP_TYPE of
+// such a record is not MT_OP_INSERT).
 __global__ void mt_fixup_kernel(mt_gstate g, const mt_op_rec* __restrict__ ops, uint32_t n_docs) {
     const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n_docs) return;

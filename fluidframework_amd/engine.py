@@ -38,6 +38,12 @@ POS_RESULT_DTYPE = np.dtype([('ordinal', '<i4'), ('offset', '<i4'), ('position',
 POS_CONTAINING, POS_OF_ORDINAL, POS_LOCAL = 0, 1, -2**31
 assert POS_QUERY_DTYPE.itemsize == 16 and POS_RESULT_DTYPE.itemsize == 16
 assert TILE_QUERY_DTYPE.itemsize == 48
+# mt_marker_query / mt_marker_result (include/mtgpu.h "marker ids"): posFromRelativePos queries
+MARKER_QUERY_DTYPE = np.dtype([('doc', '<u4'), ('ref_seq', '<i4'), ('client', '<u2'), ('key', 'u1'), ('pad', 'u1'),
+                               ('value', '<u2'), ('pad2', '<u2')])
+MARKER_RESULT_DTYPE = np.dtype([('ordinal', '<i4'), ('position', '<i4'), ('flags', '<u4'), ('length', '<u4')])
+MKF_HIDDEN, MKF_TOMBSTONE = 1, 2
+assert MARKER_QUERY_DTYPE.itemsize == 16 and MARKER_RESULT_DTYPE.itemsize == 16
 # mt_stack_item (include/mtgpu.h "range stacks")
 STACK_ITEM_DTYPE = np.dtype([('pos', '<i4'), ('ordinal', '<i4'), ('ref_type', '<u4')])
 
@@ -100,6 +106,10 @@ def lib():
                                        vp]
         L.mt_find_tiles.argtypes = [vp, vp, u32, vp]
         for name in ('mt_resolve_positions', 'mt_resolve_positions_device'):  # (absent from older A/B builds)
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [vp, vp, u32, vp]
+                getattr(L, name).restype = ctypes.c_int
+        for name in ('mt_marker_positions', 'mt_marker_positions_device'):  # (absent from older A/B builds)
             if hasattr(L, name):
                 getattr(L, name).argtypes = [vp, vp, u32, vp]
                 getattr(L, name).restype = ctypes.c_int
@@ -315,6 +325,21 @@ class MergeEngine:
         """mt_resolve_positions_device: device-resident POS_QUERY_DTYPE rows -> POS_RESULT_DTYPE rows
         (device pointers as ints; asynchronous on the engine's stream, complete after sync())."""
         _check(lib().mt_resolve_positions_device(self.h, d_queries, n, d_out), 'mt_resolve_positions_device')
+        _check(lib().mt_sync(self.h), 'mt_sync')
+
+    def marker_positions(self, queries):
+        """MergeTree.posFromRelativePos' lookup for a batch of MARKER_QUERY_DTYPE rows
+        (mt_marker_positions): MARKER_RESULT_DTYPE rows -- the marker an id names (ordinal -1: none)
+        and its position in the view; relpos.position_of forms the relative position from a row."""
+        q = np.ascontiguousarray(queries, dtype=MARKER_QUERY_DTYPE)
+        out = np.zeros(len(q), dtype=MARKER_RESULT_DTYPE)
+        _check(lib().mt_marker_positions(self.h, _ptr(q), len(q), _ptr(out)), 'mt_marker_positions')
+        return out
+
+    def marker_positions_device(self, d_queries, n, d_out):
+        """mt_marker_positions_device: device-resident MARKER_QUERY_DTYPE rows -> MARKER_RESULT_DTYPE
+        rows (device pointers as ints; complete on return)."""
+        _check(lib().mt_marker_positions_device(self.h, d_queries, n, d_out), 'mt_marker_positions_device')
         _check(lib().mt_sync(self.h), 'mt_sync')
 
     def regen_drain(self, doc):

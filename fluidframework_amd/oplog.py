@@ -55,6 +55,72 @@ def encode_text(text, force_wide=False):
 def decode_text(b, wide):
     return b.decode('utf-16-le', 'surrogatepass') if wide else b.decode('latin-1')
 
+# Marker-relative ends (include/mtgpu.h "marker-relative positions"): two bits inside the 5-bit type
+# field, and per relative end one 8-byte block at the payload's tail, after the pairs, pos1's first:
+# {key u8, flags u8 (bit 0: before), value id u16 LE, offset i32 LE}.
+OP_REL1, OP_REL2 = 0x08, 0x10
+OP_REL = OP_REL1 | OP_REL2
+REL_BYTES = 8
+REL_BEFORE = 1
+
+
+def base_type(typ):
+    """MT_OP_BASE: the type proper of a record's type byte."""
+    return int(typ) & 0x07
+
+
+def rel_len(typ):
+    """MT_OP_REL_LEN: bytes of the relative ends' blocks."""
+    return (REL_BYTES if int(typ) & OP_REL1 else 0) + (REL_BYTES if int(typ) & OP_REL2 else 0)
+
+
+def tail_len(typ, flags):
+    """MT_OP_PAIRS_LEN: bytes of the payload's tail, the pairs and the relative ends' blocks."""
+    return (3 if int(typ) & OP_WIDE else 2) * npairs(flags, typ) + rel_len(typ)
+
+
+def rel_block(key, value, before=False, offset=0):
+    """One relative end: the marker whose property `key` (the document's id of "markerId") holds value
+    id `value`; before it or after it, `offset` further away."""
+    if not (0 <= key < 256 and 0 <= value < 65536 and -2**31 <= offset < 2**31):
+        raise ValueError('relative end out of range: key %r, value id %r, offset %r' % (key, value, offset))
+    return struct.pack('<BBHi', key, REL_BEFORE if before else 0, value, offset)
+
+
+def parse_rel_block(b):
+    key, fl, value, offset = struct.unpack('<BBHi', bytes(b))
+    return {'key': key, 'value': value, 'before': bool(fl & REL_BEFORE), 'offset': offset}
+
+
+def rel_record(body, typ, rel1=None, rel2=None):
+    """(type byte, payload) of a record whose payload without relative ends is `body` ([text][pairs])
+    and whose type byte is `typ`: the blocks of rel1 / rel2 (rel_block bytes, or None for an absolute
+    end) appended, the type's bits set.  The record's pos field of a relative end is 0."""
+    t = int(typ) & ~OP_REL
+    out = bytes(body)
+    for bit, blk in ((OP_REL1, rel1), (OP_REL2, rel2)):
+        if blk is not None:
+            if len(blk) != REL_BYTES:
+                raise ValueError('a relative end is %d bytes' % REL_BYTES)
+            t |= bit
+            out += bytes(blk)
+    return t, out
+
+
+def split_payload(rec, payload):
+    """(text bytes, pairs bytes, rel1 | None, rel2 | None) of a record; the relative ends as
+    parse_rel_block dicts.  ValueError when the payload is shorter than its tail."""
+    typ, off, ln = int(rec['type']), int(rec['payload_off']), int(rec['payload_len'])
+    tl, rl = tail_len(typ, rec['flags']), rel_len(typ)
+    if ln < tl or off + ln > len(payload):
+        raise ValueError('payload of %d bytes is shorter than its tail of %d' % (ln, tl))
+    body = bytes(payload[off:off + ln])
+    blocks = [body[ln - rl + REL_BYTES * i:ln - rl + REL_BYTES * (i + 1)] for i in range(rl // REL_BYTES)]
+    rel1 = parse_rel_block(blocks.pop(0)) if typ & OP_REL1 else None
+    rel2 = parse_rel_block(blocks.pop(0)) if typ & OP_REL2 else None
+    return body[:ln - tl], body[ln - tl:ln - rl], rel1, rel2
+
+
 MAGIC = b'MTLOG001'
 
 
@@ -141,6 +207,42 @@ class OpBatch:
             idx = np.concatenate([np.arange(a, c) for a, c in zip(lo, hi)]) if n.sum() else np.zeros(0, np.int64)
             out.append(OpBatch(self.ops[idx], self.payload, rp))
         return out
+
+
+def encode_record(typ, flags=0, text=None, props=None, rel1=None, rel2=None, force_wide=False):
+    """(type byte, flags byte, payload bytes) of one record as a host writes it: `typ` the base type,
+    `text` a str (a Marker's one character is its refType), `props` {key id: value id | None} or None,
+    rel1 / rel2 relative ends as {key, value, before, offset} dicts (or None: the end is absolute).
+    The record goes out wide (MT_OP_WIDE) when its text, keys or value ids need it."""
+    tb, wide = encode_text(text or '', force_wide)
+    wide = wide or any(k >= 8 or (v or 0) > 255 for k, v in (props or {}).items())
+    if wide:
+        tb, _ = encode_text(text or '', force_wide=True)
+    pairs = b''
+    for k, v in (props or {}).items():
+        v = 0 if v is None else v
+        pairs += bytes([k, v & 0xFF, v >> 8]) if wide else bytes([k, v])
+    if props is not None and typ == INSERT:
+        flags |= F_PROPS
+    fbits, tbits = pack_npairs(len(props or {}), wide)
+    blocks = [None if r is None else rel_block(r['key'], r['value'], r.get('before', False), r.get('offset', 0))
+              for r in (rel1, rel2)]
+    t, data = rel_record(tb + pairs, typ | (OP_WIDE if wide else 0) | tbits, *blocks)
+    return t, flags | fbits, data
+
+
+def build_batch(docs):
+    """OpBatch of documents given as lists of (seq, ref, msn, client, type, pos1, pos2, text, props,
+    flags[, rel1, rel2]) tuples (encode_record's arguments)."""
+    recs, payload, row_ptr = [], bytearray(), [0]
+    for ops in docs:
+        for (seq, ref, msn, client, typ, p1, p2, text, props, flags, *rel) in ops:
+            t, fl, data = encode_record(typ, flags, text, props, *rel)
+            recs.append((seq, ref, msn, client, t, fl, p1, p2, len(payload), len(data)))
+            payload += data
+        row_ptr.append(len(recs))
+    return OpBatch(np.array(recs, dtype=OP_DTYPE), np.frombuffer(bytes(payload), dtype=np.uint8),
+                   np.array(row_ptr, dtype=np.uint32))
 
 
 def synth_cfg_array(seed=1, n_clients=8, ops_per_doc=1024, max_lag=8, stall_ops=0, n_keys=0, n_values=16,

@@ -68,10 +68,51 @@ enum mt_op_flags {
  * good (see "limits" below); narrow-form ops apply to wide documents unchanged. */
 #define MT_OP_WIDE 0x80u
 #define MT_OP_TYPE(o) ((o).type & 0x1Fu)
+/* Marker-relative positions (ops.ts IRelativePosition; Client.getValidOpRange, client.ts:485-502 ->
+ * MergeTree.posFromRelativePos, mergeTree.ts:1943-1966): an INSERT / REMOVE / ANNOTATE whose pos1
+ * (pos2) is given as "before / after the marker with this id" -- what Client.annotateMarker sends
+ * (opBuilder.ts:25-39: relativePos1 {id, before: true}, relativePos2 {id}).  Every receiver resolves
+ * it against its own tree when it applies the op, so the record carries the marker's name, not a
+ * position.  Two bits inside the 5-bit type field say which ends are relative; MT_OP_BASE is the
+ * type proper, and MT_OP_TYPE of such a record is none of the mt_op_type values (an engine form that
+ * does not know them refuses the record as malformed).  Each relative end adds one 8-byte block at
+ * the payload's tail, after the pairs, pos1's first:
+ *     {key u8, flags u8 (bit 0: before), value id u16 LE, offset i32 LE}
+ * key / value id are the document's interned ids of the "markerId" property and of the id string
+ * (always a u16, in narrow and wide records alike); the `pos` field of a relative end is 0.
+ * Which marker: among the document's linked segments -- tombstones included -- the Markers whose
+ * current value of `key` is `value id`; of these the one with the greatest insert seq (an editing
+ * client's pending insert above every sequenced one), the last in document order among equals
+ * (mt_marker.h).  Value id 0 names no marker.  With p the marker's position in the op's view
+ * (refSeq, client) -- the view lengths of the leaves before it, whether or not the view shows the
+ * marker itself -- the end is p - offset (before) or p + 1 + offset.
+ *   no marker, REMOVE / ANNOTATE with both ends relative and unresolved: the reference's range
+ *     (-1, -1): no split, no segment touched, the callback fires without segments, zamboni, the
+ *     window asserts and updateSeqNumbers run;
+ *   no marker for an INSERT, a resolved position below 0, or one unresolved end beside a resolved or
+ *     absolute one: MT_DERR_BAD_OP, as negative absolute positions are;
+ *   seq = MT_SEQ_LOCAL / MT_SEQ_REGEN, a second relative end on an INSERT, or a base type past
+ *     ANNOTATE: MT_DERR_BAD_OP (an editing client's host resolves its own edits in its local view and
+ *     sends absolute records; its sequenced relative record is the ack of that edit).
+ * A launch holding such a record runs its document on the LDS engine for that launch.
+ * Kept differences from the reference, whose idToSegment map is filled at insert / load time
+ * (mergeTree.ts:279-283, 2074-2078, 2200-2204) and never updated: with duplicate ids the reference
+ * answers with whichever marker that replica inserted last (its replicas can disagree; the rule
+ * above is the engine's); an annotate that rewrites "markerId" itself is followed here (current
+ * props) and ignored there; a marker zamboni has unlinked is not found here, while the reference
+ * walks up from its stale parent. */
+#define MT_OP_REL1 0x08u
+#define MT_OP_REL2 0x10u
+#define MT_OP_REL (MT_OP_REL1 | MT_OP_REL2)
+#define MT_OP_BASE(o) ((o).type & 0x07u)
+#define MT_REL_BYTES 8u
+#define MT_REL_BEFORE 1u
+#define MT_OP_REL_LEN(o) ((((o).type & MT_OP_REL1) ? MT_REL_BYTES : 0u) + (((o).type & MT_OP_REL2) ? MT_REL_BYTES : 0u))
 #define MT_OP_PAIR_BYTES(o) (((o).type & MT_OP_WIDE) ? 3u : 2u)
-#define MT_OP_PAIRS_LEN(o) (MT_OP_PAIR_BYTES(o) * MT_OP_NPAIRS(o))
-/* a remove or annotate record carries no text: its payload is exactly its pairs (else MT_DERR_BAD_OP) */
-#define MT_OP_NO_TEXT_OK(o) ((MT_OP_TYPE(o) != MT_OP_REMOVE && MT_OP_TYPE(o) != MT_OP_ANNOTATE) || \
+/* the payload's tail: the pairs and, after them, the relative ends' blocks */
+#define MT_OP_PAIRS_LEN(o) (MT_OP_PAIR_BYTES(o) * MT_OP_NPAIRS(o) + MT_OP_REL_LEN(o))
+/* a remove or annotate record carries no text: its payload is exactly its tail (else MT_DERR_BAD_OP) */
+#define MT_OP_NO_TEXT_OK(o) ((MT_OP_BASE(o) != MT_OP_REMOVE && MT_OP_BASE(o) != MT_OP_ANNOTATE) || \
                              (o).payload_len == MT_OP_PAIRS_LEN(o))
 /* An insert whose segment spec is the empty string is dropped by Client.applyInsertOp before it
  * touches the tree (`if (op.seg)`, client.ts:403-407: no boundary split, no completeAndLogOp
@@ -79,9 +120,11 @@ enum mt_op_flags {
  * text bytes) is applied exactly as an MT_OP_NOOP.  An empty text WITH a props object is a real
  * insert: the boundary split happens and blockInsert skips the zero-length segment. */
 #define MT_OP_IS_EMPTY_INSERT(o)                                                      \
-    (MT_OP_TYPE(o) == MT_OP_INSERT && !((o).flags & (MT_F_PROPS | MT_F_MARKER)) &&    \
+    (MT_OP_BASE(o) == MT_OP_INSERT && !((o).flags & (MT_F_PROPS | MT_F_MARKER)) &&    \
      (o).payload_len <= MT_OP_PAIRS_LEN(o))
-#define MT_OP_IS_NOOP(o) (MT_OP_TYPE(o) == MT_OP_NOOP || MT_OP_IS_EMPTY_INSERT(o))
+/* (by base type: a relative insert of the empty string is dropped like an absolute one,
+ * getValidOpRange has no effect of its own) */
+#define MT_OP_IS_NOOP(o) (MT_OP_BASE(o) == MT_OP_NOOP || MT_OP_IS_EMPTY_INSERT(o))
 /* An editing client.  A record with seq = MT_SEQ_LOCAL is a local edit of the
  * document's editing client (insertSegmentLocal / removeRangeLocal / annotateRangeLocal,
  * client.ts:163-214): INSERT / REMOVE / ANNOTATE at positions of its local view, applied at once
@@ -473,6 +516,39 @@ mt_status mt_text_ranges_device(mt_engine* eng, const mt_text_query* d_q, uint32
  * a placeholder, units is MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1577-1579); without
  * one, that less the view's markers. */
 mt_status mt_text_lengths(mt_engine* eng, const mt_text_query* q, uint32_t n, mt_text_count* out);
+
+/* ---- marker ids ---------------------------------------------------------------------------------
+ * MergeTree.posFromRelativePos(relativePos, refseq, clientId) (mergeTree.ts:1943-1966;
+ * Client.posFromRelativePos, client.ts:307-309, uses the local view) for a batch of queries, one wave
+ * per query over the document's state in HBM: which linked Marker holds value id `value` under key
+ * `key` ("marker-relative positions" above: tombstones count, the one inserted last wins, then the
+ * last in document order; value 0 names none) and its position in the view -- getPosition(marker,
+ * refSeq, clientId), the view lengths of the leaves before it.  The caller forms
+ * position - offset (before) or position + length + offset.  The view is (ref_seq, client) or, with
+ * ref_seq = MT_POS_LOCAL, the local view, exactly as for mt_pos_query.  Stream-ordered after every
+ * submitted op; a document with a sticky error answers from its state before the failing message. */
+#define MT_MKF_HIDDEN 1u      /* mt_marker_result.flags: the marker has no length in the view */
+#define MT_MKF_TOMBSTONE 2u   /* it is removed (a sequenced or a pending removal) */
+typedef struct mt_marker_query {  /* 16 bytes */
+    uint32_t doc;
+    int32_t ref_seq;            /* the view's refSeq, or MT_POS_LOCAL */
+    uint16_t client;            /* the view's short client id (ignored for MT_POS_LOCAL) */
+    uint8_t key;                /* the document's key id of "markerId" (< MT_MAX_KEYS_WIDE) */
+    uint8_t pad;
+    uint16_t value;             /* the id string's value id under that key */
+    uint16_t pad2;
+} mt_marker_query;
+typedef struct mt_marker_result { /* 16 bytes */
+    int32_t ordinal;            /* the marker's index among the linked segments, -1: none */
+    int32_t position;           /* its position in the view (0 without a marker) */
+    uint32_t flags;             /* MT_MKF_* */
+    uint32_t length;            /* its cachedLength (1; 0 without a marker) */
+} mt_marker_result;
+/* MT_ERR_ARG: a document past the engine's, or key >= MT_MAX_KEYS_WIDE */
+mt_status mt_marker_positions(mt_engine* eng, const mt_marker_query* q, uint32_t n, mt_marker_result* out);
+/* the same with device-resident queries and results (asynchronous on the engine's stream); a query the
+ * host could not check gets ordinal MT_POS_BAD_QUERY and reads nothing */
+mt_status mt_marker_positions_device(mt_engine* eng, const mt_marker_query* d_q, uint32_t n, mt_marker_result* d_out);
 
 /* The ops document `doc` regenerated at its MT_SEQ_REGEN records since the last drain (at most 256
  * records / 4 KiB of payload between drains, else MT_DERR_CAPACITY): per regenerated op one

@@ -35,6 +35,8 @@ const { TextHelper } = require(path.join(__dirname, "textHelper.js"));
 const INSERT = 0, REMOVE = 1, ANNOTATE = 2, GROUP = 3, NOOP = 3;
 const F_REWRITE = 1, F_PROPS = 2, F_GROUP_MORE = 4, F_MARKER = 128;
 const OP_WIDE = 0x80;  // MT_OP_WIDE: UTF-16 text, (key u8, value u16) pairs
+const OP_REL1 = 0x08, OP_REL2 = 0x10;  // MT_OP_REL1 / MT_OP_REL2: pos1 / pos2 is relative to a marker (8-byte block at the payload's tail)
+const REL_BYTES = 8, REL_BEFORE = 1;
 const OP_NP16 = 0x40;  // MT_OP_NP16: property pair count bit 4 (wide records)
 const OP_NP32 = 0x20;  // MT_OP_NP32: property pair count bit 5 (wide records)
 // mt_pos_query (include/mtgpu.h): kinds, and the local view's refSeq
@@ -264,24 +266,45 @@ class BatchClient {
         return id;
     }
 
+    _keyId(k) {
+        let kid = this.keyIds.get(k);
+        if (kid === undefined) {
+            kid = this.keys.length;
+            if (kid >= MAX_KEYS) throw new Error(`BatchClient: more than ${MAX_KEYS} property keys`);
+            this.keyIds.set(k, kid);
+            this.keys.push(k);
+            this.valueIds.push(new Map());
+            this.values.push([undefined]);
+            // the label keys whose block caches the engine tracks (mt_set_label_keys), declared
+            // before the batch that carries the key's first op is submitted (BatchEngine._encode)
+            if (k === "referenceTileLabels" || k === "referenceRangeLabels") {
+                this.engine.labelDecl.push([this.doc, k === "referenceTileLabels" ? kid : -1,
+                    k === "referenceRangeLabels" ? kid : -1]);
+            }
+        }
+        return kid;
+    }
+
+    // One relative end's block (include/mtgpu.h "marker-relative positions"): the ids of the "markerId"
+    // key and of rel.id under it -- interned like any property value, so an id no marker carries gets
+    // an id no segment holds and resolves to nothing, as in the reference (mergeTree.ts:1943-1966)
+    _rel(rel) {
+        const b = Buffer.alloc(REL_BYTES);
+        const offset = rel.offset === undefined ? 0 : rel.offset;
+        if (!Number.isInteger(offset) || offset < -0x80000000 || offset > 0x7fffffff) throw new Error("BatchClient: relative offset out of range");
+        const kid = this._keyId("markerId");
+        const vid = rel.id === undefined || rel.id === null || rel.id === "" ? 0 : this._pairs({ markerId: rel.id })[1];
+        b.writeUInt8(kid, 0);
+        b.writeUInt8(rel.before ? REL_BEFORE : 0, 1);
+        b.writeUInt16LE(vid, 2);
+        b.writeInt32LE(offset, 4);
+        return b;
+    }
+
     _pairs(props) {
         const out = [];
         for (const k of Object.keys(props || {})) {
-            let kid = this.keyIds.get(k);
-            if (kid === undefined) {
-                kid = this.keys.length;
-                if (kid >= MAX_KEYS) throw new Error(`BatchClient: more than ${MAX_KEYS} property keys`);
-                this.keyIds.set(k, kid);
-                this.keys.push(k);
-                this.valueIds.push(new Map());
-                this.values.push([undefined]);
-                // the label keys whose block caches the engine tracks (mt_set_label_keys), declared
-                // before the batch that carries the key's first op is submitted (BatchEngine._encode)
-                if (k === "referenceTileLabels" || k === "referenceRangeLabels") {
-                    this.engine.labelDecl.push([this.doc, k === "referenceTileLabels" ? kid : -1,
-                        k === "referenceRangeLabels" ? kid : -1]);
-                }
-            }
+            const kid = this._keyId(k);
             const v = props[k];
             let vid = 0;
             if (v !== null) {
@@ -309,7 +332,7 @@ class BatchClient {
             client, type: NOOP, flags: more ? F_GROUP_MORE : 0, npairs: 0, pos1: 0, pos2: 0, payload: Buffer.alloc(0) };
         if (!op) return r;
         if (op.type === INSERT) {
-            if (op.register || op.relativePos1) throw new Error("BatchClient: register/relative inserts unsupported");
+            if (op.register) throw new Error("BatchClient: register inserts unsupported");
             if (op.seg === "") return r;  // `if (op.seg)`: dropped before the tree (client.ts:403-407)
             let text, pairs = [];
             if (typeof op.seg === "string") text = op.seg;
@@ -327,13 +350,15 @@ class BatchClient {
             if (typeof text !== "string") throw new Error("BatchClient: segment text must be a string");
             // lengths and positions are UTF-16 code units (cachedLength = text.length, textSegment.ts:45):
             // Latin-1 bytes when every unit fits, else the wide form's 2 bytes per unit
-            r.type = INSERT; r.pos1 = op.pos1;
+            r.type = INSERT; r.pos1 = op.pos1 === undefined && op.relativePos1 ? 0 : op.pos1;
             r.npairs = pairs.length / 2;
             r.text = text;
             r.pairs = pairs;
         } else if (op.type === REMOVE || op.type === ANNOTATE) {
-            if (op.relativePos1 || op.relativePos2 || op.register) throw new Error("BatchClient: unsupported op form");
-            r.type = op.type; r.pos1 = op.pos1; r.pos2 = op.pos2;
+            if (op.register) throw new Error("BatchClient: unsupported op form");
+            r.type = op.type;
+            r.pos1 = op.pos1 === undefined && op.relativePos1 ? 0 : op.pos1;
+            r.pos2 = op.pos2 === undefined && op.relativePos2 ? 0 : op.pos2;
             if (op.type === ANNOTATE) {
                 if (op.combiningOp) {
                     if (op.combiningOp.name !== "rewrite") throw new Error("BatchClient: combining ops unsupported");
@@ -363,6 +388,16 @@ class BatchClient {
             }
             delete r.text;
             delete r.pairs;
+        }
+        // getValidOpRange (client.ts:485-502): an end without a position and with a relative one is
+        // resolved by the receiver -- on the device: its block goes to the payload's tail, pos1's first
+        const rel1 = op.pos1 === undefined ? op.relativePos1 : undefined;
+        const rel2 = op.type !== INSERT && op.pos2 === undefined ? op.relativePos2 : undefined;
+        if (r.type !== NOOP && (rel1 || rel2)) {
+            const parts = [r.payload];
+            if (rel1) { parts.push(this._rel(rel1)); r.type |= OP_REL1; }
+            if (rel2) { parts.push(this._rel(rel2)); r.type |= OP_REL2; }
+            r.payload = Buffer.concat(parts);
         }
         return r;
     }
@@ -441,6 +476,48 @@ class BatchClient {
         return ops.length === 1 ? ops[0] : { type: GROUP, ops };
     }
 
+    /**
+     * Client.posFromRelativePos (client.ts:307-309 -> mergeTree.ts:1943-1966) in the local view, over the
+     * device's marker query (mt_marker_positions): -1 when no linked marker carries the id.
+     */
+    posFromRelativePos(relativePos, refSeq, clientId) {
+        const m = this._marker(relativePos.id, refSeq, clientId);
+        if (m.ordinal < 0) return -1;
+        const offset = relativePos.offset === undefined ? 0 : relativePos.offset;
+        return relativePos.before ? m.position - offset : m.position + m.length + offset;
+    }
+    _marker(id, refSeq, clientId) {
+        this.engine.flush();
+        this._checkError();
+        const kid = this.keyIds.get("markerId");
+        const vid = kid === undefined || id === undefined ? undefined : this.valueIds[kid].get(canonicalJson(id));
+        if (vid === undefined) return { ordinal: -1, position: 0, flags: 0, length: 0 };  // no segment can hold it
+        const q = Buffer.alloc(16);
+        q.writeUInt32LE(this.doc, 0);
+        q.writeInt32LE(refSeq === undefined ? POS_LOCAL : refSeq, 4);
+        q.writeUInt16LE(clientId || 0, 8);
+        q.writeUInt8(kid, 10);
+        q.writeUInt16LE(vid, 12);
+        const r = native.markerPositions(this.engine.handle, q);
+        return { ordinal: r.readInt32LE(0), position: r.readInt32LE(4), flags: r.readUInt32LE(8), length: r.readUInt32LE(12) };
+    }
+    /**
+     * Client.annotateMarker (client.ts:142-154) for an editing client: the op in the reference's relative
+     * form (opBuilder.ts:25-39), undefined when the marker has no id or the range is invalid in the local
+     * view (getValidOpRange, client.ts:507-543).  The local edit is queued in absolute form: the range the
+     * local view gives.
+     */
+    annotateMarker(marker, props, combiningOp) {
+        const id = marker && marker.properties ? marker.properties.markerId : undefined;
+        if (!id) return undefined;
+        const op = { combiningOp, props, relativePos1: { id, before: true }, relativePos2: { id }, type: ANNOTATE };
+        const start = this.posFromRelativePos(op.relativePos1), end = this.posFromRelativePos(op.relativePos2);
+        const length = this.getLength();
+        if (start < 0 || start >= length || end <= start) return undefined;
+        if (!this._local({ type: ANNOTATE, pos1: start, pos2: end, props, combiningOp })) return undefined;
+        if (this.engine.recording) this.expect[this.expect.length - 1].op = op;  // (the callback's opArgs.op)
+        return op;
+    }
     /** Client.removeRangeLocal (client.ts:188-195). */
     removeRangeLocal(start, end) { return this._local({ type: REMOVE, pos1: start, pos2: end }); }
     /** Client.annotateRangeLocal (client.ts:163-179). */

@@ -389,6 +389,28 @@ static napi_value resolve_positions(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* markerPositions(engine, queries (16-byte mt_marker_query rows)) -> Buffer of 16-byte mt_marker_result rows */
+static napi_value marker_positions(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], out;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 2 ? get_box(env, argv[0]) : NULL;
+    size_t nq = 0;
+    const void* q = b ? buffer_data(env, argv[1], &nq) : NULL;
+    if (!b || nq % sizeof(mt_marker_query)) {
+        napi_throw_type_error(env, NULL, "markerPositions(engine, queries)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(nq / sizeof(mt_marker_query));
+    void* data = NULL;
+    NAPI_CALL(env, napi_create_buffer(env, n ? n * sizeof(mt_marker_result) : 1, &data, &out));
+    enter(b);
+    mt_status st = mt_marker_positions(b->e, (const mt_marker_query*)q, n, (mt_marker_result*)data);
+    leave(b);
+    if (st) return throw_status(env, "mt_marker_positions", st);
+    return out;
+}
+
 /* segmentInfos(engine, docs (uint32 rows), ordinals (int32 rows)) -> Buffer of 104-byte mt_seg_info rows */
 static napi_value segment_infos(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -891,6 +913,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setLabelKeys", NULL, set_label_keys, NULL, NULL, NULL, napi_default, NULL},
         {"rangeStacks", NULL, range_stacks, NULL, NULL, NULL, napi_default, NULL},
         {"resolvePositions", NULL, resolve_positions, NULL, NULL, NULL, napi_default, NULL},
+        {"markerPositions", NULL, marker_positions, NULL, NULL, NULL, napi_default, NULL},
         {"segmentInfos", NULL, segment_infos, NULL, NULL, NULL, napi_default, NULL},
         {"segmentText", NULL, segment_text, NULL, NULL, NULL, napi_default, NULL},
         {"regenDrain", NULL, regen_drain, NULL, NULL, NULL, napi_default, NULL},

@@ -3,6 +3,9 @@
 // objects (protocol.ts:132-172) carrying IMergeTreeOp contents (ops.ts:63-110).  Client long ids
 // are "c<id>" for record client <id>; property keys "k<id>", values the value ids.  A marker insert
 // (flags bit 7) carries its ReferenceType as the one text byte: seg = {marker: {refType}, props?}.
+// A record with marker-relative ends (type bits 3 / 4, include/mtgpu.h) becomes an op with relativePos1 /
+// relativePos2 {id, before, offset?} in place of pos1 / pos2: with opts.markerKey = k, key k is the
+// reserved "markerId" property and its value id v the id "m<v>".
 const fs = require("fs");
 
 function loadLog(file) {
@@ -42,28 +45,46 @@ const pairBytes = (r) => (r.type & 0x80 ? 3 : 2);
 // property pairs: flags bits 3..6, plus 16 when type bit 6 (MT_OP_NP16) is set, 32 when type bit 5
 // (MT_OP_NP32) is
 const npairsOf = (r) => ((r.flags >> 3) & 15) | (r.type & 0x40 ? 16 : 0) | (r.type & 0x20 ? 32 : 0);
+// the relative ends' 8-byte blocks at the payload's tail: {key u8, flags u8 (bit 0: before), value u16, offset i32}
+const relLen = (r) => (r.type & 0x08 ? 8 : 0) + (r.type & 0x10 ? 8 : 0);
+function relOf(log, r, second) {
+    const at = log.payOff + r.poff + r.plen - relLen(r) + (second && (r.type & 0x08) ? 8 : 0);
+    const rel = { id: "m" + log.buf.readUInt16LE(at + 2) };
+    if (log.buf.readUInt8(at + 1) & 1) rel.before = true;
+    const offset = log.buf.readInt32LE(at + 4);
+    if (offset !== 0) rel.offset = offset;
+    return rel;
+}
 function textOf(log, r) {
     const np = npairsOf(r);
-    const a = log.payOff + r.poff, b = a + r.plen - pairBytes(r) * np;
+    const a = log.payOff + r.poff, b = a + r.plen - pairBytes(r) * np - relLen(r);
     return log.buf.toString(r.type & 0x80 ? "utf16le" : "latin1", a, b);
 }
 
 function propsOf(log, r, opts) {
     const np = npairsOf(r), pb = pairBytes(r);
-    const start = log.payOff + r.poff + r.plen - pb * np;
+    const start = log.payOff + r.poff + r.plen - pb * np - relLen(r);
     const props = {};
     for (let q = 0; q < np; q++) {
         const k = log.buf.readUInt8(start + pb * q);
         const v = pb === 3 ? log.buf.readUInt16LE(start + 3 * q + 1) : log.buf.readUInt8(start + 2 * q + 1);
         if (opts && opts.tileKey === k) props.referenceTileLabels = v === 0 ? null : tileLabels(v);
         else if (opts && opts.rangeKey === k) props.referenceRangeLabels = v === 0 ? null : tileLabels(v);
+        else if (opts && opts.markerKey === k) props.markerId = v === 0 ? null : "m" + v;
         else props["k" + k] = v === 0 ? null : v;
     }
     return props;
 }
 
 function toOp(log, r, opts) {
-    const type = r.type & 0x1f;
+    const op = absOp(log, r, opts);
+    if (op && (r.type & 0x08)) { delete op.pos1; op.relativePos1 = relOf(log, r, false); }
+    if (op && (r.type & 0x10)) { delete op.pos2; op.relativePos2 = relOf(log, r, true); }
+    return op;
+}
+
+function absOp(log, r, opts) {
+    const type = r.type & 0x07;
     if (type === 0 && (r.flags & 128)) {
         const seg = { marker: { refType: textOf(log, r).charCodeAt(0) } };
         if (r.flags & 2) seg.props = propsOf(log, r, opts);
