@@ -798,8 +798,16 @@ struct Wave {
             }
         }
         if (k < 0) return true;
+        return split_leaf<true>(k, pos - cstart(k), pos, seq);
+    }
+
+    // splitLeafSegment (mergeTree.ts:2225-2239) of the leaf at position k at offset off, and the link
+    // of its right half behind it in the same block (insertingWalk's, or insertAtReferencePosition's
+    // insertChildNode + rebalanceTree, mergeTree.ts:2048-2051).  CUM: cum[] stays valid for the view
+    // it was scanned for, in which the split falls at position pos.
+    template <bool CUM>
+    MT_DEV bool split_leaf(int k, int off, int pos, int32_t seq) {
         const int sl = s.order[k];
-        const int off = pos - cstart(k);
         const int t = alloc_slot(seq);
         if (t < 0) return false;
         block_starts();
@@ -829,10 +837,12 @@ struct Wave {
             const TC last = arena[s.toff[sl] + (uint32_t)off - 1];
             s.flags[sl] = (uint8_t)((s.flags[sl] & ~MT_SF_NL) | (last == '\n' ? MT_SF_NL : 0));
         }
-        const int old_end = s.cum[k];
+        const int old_end = CUM ? s.cum[k] : -1;
         sync();
-        if (lane == 0) s.cum[k] = pos;
-        sync();
+        if constexpr (CUM) {
+            if (lane == 0) s.cum[k] = pos;
+            sync();
+        }
         // MergeTreeMaintenanceType.SPLIT (mergeTree.ts:2231-2236): [segment, next-to-be-linked]
         emit(MT_EV_SPLIT, MT_EVF_FIRST, k, -1, (uint32_t)off);
         emit(MT_EV_SPLIT, 0, k + 1, -1, s.len[t]);
@@ -1114,6 +1124,75 @@ struct Wave {
     }
 
     // -------------------------------------------------------------------- ops
+    // op_insert_at's new segment (TextSegment.make / Marker, its text in the arena, its stamps and its
+    // pending group: saveIfLocal), not yet linked; -1: the document halted.  The same lines as
+    // op_insert's, which keeps its own: sharing them moved the register counts of every other form
+    // 
+    MT_DEV int new_leaf(const mt_op_rec& op, const uint8_t* pay, int tlen, const Pairs& pr, int32_t S, int C) {
+        const int t = alloc_slot(S);
+        if (t < 0) return -1;
+        if (!arena_reserve((uint32_t)tlen, S)) return -1;
+        const uint32_t top = s.text_top;
+        bool hasnl = false;
+        const bool wop = (op.type & MT_OP_WIDE) != 0;  // the payload text is UTF-16 code units
+        auto unit = [&](int i) -> uint32_t {
+            return wop ? (uint32_t)pay[2 * i] | ((uint32_t)pay[2 * i + 1] << 8) : (uint32_t)pay[i];
+        };
+        for (int base = 0; base < tlen; base += 64) {
+            const int i = base + lane;
+            uint32_t c = 0;
+            if (i < tlen) {
+                c = unit(i);
+                arena[top + i] = (TC)c;
+            }
+            hasnl = hasnl || wave_ballot(i < tlen && c == '\n') != 0;
+        }
+        __threadfence_block();
+        if (lane == 0) {
+            // a snapshot body segment may arrive removed (SnapshotLoader.specToSegment,
+            // snapshotLoader.ts:101-106): MT_OP_LOAD carries removedSeq in pos2
+            const bool lrm = MT_OP_TYPE(op) == MT_OP_LOAD && op.pos2 >= 0;
+            s.seq[t] = S;
+            s.client[t] = (CT)C;
+            s.rseq[t] = lrm ? op.pos2 : 0;
+            s.rclient[t] = lrm ? (CT)MT_LOAD_RCLIENT(op) : 0;
+            s.ovl[t] = 0;
+            if constexpr (W)
+                ovx_zero(t);
+            s.len[t] = (uint32_t)tlen;
+            s.toff[t] = top;
+            // a Marker (MT_F_MARKER): length 1, its arena byte is its ReferenceType
+            uint8_t f = (op.flags & MT_F_MARKER) ? MT_SF_MARKER
+                                                 : ((unit(tlen - 1) == '\n' ? MT_SF_NL : 0) | (hasnl ? MT_SF_HASNL : 0));
+            f |= lrm ? MT_SF_REMOVED : 0;
+            pclear(t);
+            if (op.flags & MT_F_PROPS) {  // TextSegment.make -> addProperties
+                f |= MT_SF_PDEF;
+                papply(t, pr);
+            }
+            s.flags[t] = f;
+            if constexpr (LOC) {  // a local insert is its edit's one pending segment (saveIfLocal)
+                gm_zero(t);
+                if (S == -1) gm_set(t, s.lc.ghi);
+                pkp[t] = 0;
+                lsqp[t] = S == -1 ? (uint64_t)s.lc.lseq : 0ull;
+                s.lc.stamp = s.lc.stamp + 1;
+                const uint32_t stamp = s.lc.stamp;
+                ctp[t] = stamp;
+                ct_publish();
+                if (S == -1) {
+                    gtp[s.lc.ghi % GN] = stamp;
+                    glsp[s.lc.ghi % GN] = s.lc.lseq;
+                    ct_publish();
+                    s.lc.ghi = s.lc.ghi + 1;
+                }
+            }
+        }
+        s.text_top = top + (uint32_t)tlen;
+        sync();
+        return t;
+    }
+
     MT_DEV void op_insert(const mt_op_rec& op, const uint8_t* pay, int tlen, const Pairs& pr) {
         const int32_t S = op.seq, R = op.ref_seq;
         const bool ld = MT_OP_TYPE(op) == MT_OP_LOAD;
@@ -1257,6 +1336,49 @@ struct Wave {
             emit(MT_EV_INSERT, MT_EVF_FIRST, -1, -1, 0);  // an empty text with props: never linked
         }
         if (S != -1) zamboni();  // (a local edit runs no zamboni, mergeTree.ts:1994-1997)
+    }
+
+    // MT_OP_INSERT_AT (include/mtgpu.h "local references"): MergeTree.insertAtReferencePosition
+    // (mergeTree.ts:2042-2096) in the local view, from the reference's leaf (ordinal pos1, offset pos2,
+    // checked by apply_local) instead of a walk from the root.
+    MT_DEV void op_insert_at(const mt_op_rec& op, const uint8_t* pay, int tlen, const Pairs& pr) {
+        if constexpr (LOC) {
+            int k = op.pos1;
+            // refOffset !== 0 && refSegLen !== 0: split, the right half is the start leaf (:2047-2053)
+            if (op.pos2 != 0 && vis(s.order[k], s.cur_seq, s.lc.own) != 0) {
+                if (!split_leaf<false>(k, op.pos2, -1, -1)) return;
+                k = k + 1;
+            }
+            // leftExcursion (:2054-2068, 2280-2310): over the run of leaves of no local length in front
+            // of the start leaf, the farthest one breakTie(0, 0, leaf, currentSeq, own) holds for -- not
+            // removed, or its removal pending -- becomes the start leaf.  64 leaves per step, lane 0
+            // the nearest.
+            int start = k;
+            for (int hi = k; hi > 0; hi -= 64) {
+                const int i = hi - 1 - lane;
+                bool zero = false, tie = false;
+                if (i >= 0) {
+                    const int sl = s.order[i];
+                    const bool rm = (s.flags[sl] & MT_SF_REMOVED) != 0;
+                    zero = rm || s.len[sl] == 0;
+                    tie = !(rm && s.rseq[sl] != -1 && s.rseq[sl] <= s.cur_seq);
+                }
+                const uint64_t zm = wave_ballot(zero);
+                const int run = zm == ~0ull ? 64 : __builtin_ctzll(~zm);  // leaves of the run in this step
+                const uint64_t tm = wave_ballot(tie) & (run == 64 ? ~0ull : (1ull << run) - 1ull);
+                if (tm) start = hi - 1 - (63 - __builtin_clzll(tm));
+                if (run < 64) break;
+            }
+            // insertChildNode(startSeg.parent, segment, startSeg.index) + rebalanceTree (:2081-2083)
+            block_starts();
+            const int b = block_of_pos(start);
+            const int st = s.bst[b], c = s.lbcnt[b];
+            const int t = new_leaf(op, pay, tlen, pr, -1, s.lc.own);
+            if (t < 0) return;
+            if (!insert_at(start, b, t, -1, -1)) return;
+            refresh(st, st + c + 1);
+            if (ev) emit(MT_EV_INSERT, MT_EVF_FIRST, start, local_prefix(start), (uint32_t)tlen);
+        }
     }
 
     MT_DEV void op_range(const mt_op_rec& op, const Pairs& pr) {
@@ -1661,11 +1783,19 @@ struct Wave {
         o.ref_seq = s.cur_seq;
         s.evseq = -1;  // (a local edit's callbacks: seq -1)
         const int L = scan(o.ref_seq, C);
-        if (op.type == MT_OP_INSERT && tlen <= 0) return;  // insertSegmentLocal: nothing for an empty segment
+        bool at = false;  // an insert at a reference's leaf (MT_OP_INSERT_AT)
+        if constexpr (LOC) at = op.type == MT_OP_INSERT_AT;
+        if ((op.type == MT_OP_INSERT || at) && tlen <= 0) return;  // insertSegmentLocal: nothing for an empty segment
+        if constexpr (LOC) {
+            if (at && (o.pos1 < 0 || o.pos1 >= s.n || o.pos2 < 0 || (uint32_t)o.pos2 >= s.len[s.order[o.pos1]]))
+                return fail(MT_DERR_BAD_OP, -1);
+        }
         sync();
         s.lc.lseq = s.lc.lseq + 1;  // ++collabWindow.localSeq (mergeTree.ts:1976, 2571, 2613)
         sync();
-        if (op.type == MT_OP_INSERT) {
+        if (at) {
+            op_insert_at(o, pay, tlen, pr);
+        } else if (op.type == MT_OP_INSERT) {
             if (o.pos1 < 0 || o.pos1 > L) return fail(MT_DERR_INSERT_FAILED, -1);
             op_insert(o, pay, tlen, pr);
         } else {
@@ -1765,7 +1895,7 @@ struct Wave {
         const bool wop = (op.type & MT_OP_WIDE) != 0;
         if constexpr (LOC) {
             if (S == MT_SEQ_REGEN) return op_regen(op, payload);
-            if (type <= MT_OP_ANNOTATE && S == -1) return apply_local(op, payload);
+            if ((type <= MT_OP_ANNOTATE || type == MT_OP_INSERT_AT) && S == -1) return apply_local(op, payload);
             if (s.lc.own >= 0 && (int)op.client == s.lc.own && type <= MT_OP_ANNOTATE && !MT_OP_IS_NOOP(op))
                 return apply_ack(op, payload);
         }

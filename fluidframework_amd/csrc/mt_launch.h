@@ -82,6 +82,8 @@ hipError_t mt_launch_refs_resolve_docs(const mt_gstate* g, const uint32_t* docs,
                                        hipStream_t st);
 hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_t* docs, const uint32_t* handles, uint32_t n,
                                     uint32_t n_docs, mt_ref_pos* out, hipStream_t st);
+hipError_t mt_launch_refs_stamp(const mt_gstate* g, const uint32_t* docs, const mt_ref_pos* at, mt_op_rec* ops,
+                                uint32_t n, uint32_t n_docs, int32_t* positions, hipStream_t st);
 
 // ---- mt_intervals.hip: interval collections
 hipError_t mt_launch_intervals_overlap(const mt_gstate* g, const mt_interval_query* q, uint32_t n, uint32_t n_docs,

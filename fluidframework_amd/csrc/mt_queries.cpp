@@ -301,6 +301,43 @@ mt_status mt_refs_positions(mt_engine* e, const uint32_t* docs, const uint32_t* 
         .sync().status();
 }
 
+mt_status mt_refs_insert_local(mt_engine* e, const mt_ref_insert* at, const mt_op_rec* ops, uint32_t n,
+                               const uint8_t* payload, uint64_t payload_bytes, int32_t* positions) {
+    static_assert(sizeof(mt_ref_insert) == 8, "mt_ref_insert is 8 bytes");
+    if (!e || !e->g.refs || (n && (!at || !ops || !positions)) || (payload_bytes && !payload)) return MT_ERR_ARG;
+    std::vector<uint32_t> rows((size_t)e->n_docs + 1);
+    if (!mt_ref_insert_rows(at, ops, n, e->n_docs, payload_bytes, rows.data())) return MT_ERR_ARG;
+    if (n == 0) return MT_OK;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    std::vector<uint32_t> docs(n), handles(n);
+    for (uint32_t i = 0; i < n; i++) {
+        docs[i] = at[i].doc;
+        handles[i] = at[i].handle;
+    }
+    mt_scratch s;
+    auto [dd, dh, dat, dops, dpay, drows, dpos] = s.carve<uint32_t, uint32_t, mt_ref_pos, mt_op_rec, uint8_t, uint32_t, int32_t>(
+        n, n, n, n, std::max<uint64_t>(1, payload_bytes), rows.size(), n);
+    mt_batch b;
+    b.ops = dops;
+    b.payload = dpay;
+    b.row_ptr = drows;
+    b.n_ops = n;
+    b.payload_bytes = payload_bytes;
+    b.n_docs = e->n_docs;
+    b.max_ops_per_doc = 1;
+    return mt_chain(e->stream, s.status())
+        .h2d(dd, docs.data(), n * sizeof(uint32_t))
+        .h2d(dh, handles.data(), n * sizeof(uint32_t))
+        .h2d(dops, ops, n * sizeof *ops)
+        .h2d(dpay, payload, payload_bytes)
+        .h2d(drows, rows.data(), rows.size() * sizeof(uint32_t))
+        .call(mt_refs_positions_device, e, dd, dh, n, dat)
+        .launch(mt_launch_refs_stamp, &e->g, dd, dat, dops, n, e->n_docs, dpos, e->stream)
+        .d2h(positions, dpos, n * sizeof *positions)
+        .call(mt_batch_apply, e, &b)
+        .sync().status();
+}
+
 // ---- interval collections (include/mtgpu.h; kernels in mt_intervals.hip) -------------------------
 mt_status mt_intervals_enable(mt_engine* e, uint32_t per_doc) {
     static_assert(sizeof(mt_interval) == 16 && sizeof(mt_interval_add) == 16 && sizeof(mt_interval_query) == 16 &&

@@ -433,3 +433,42 @@ extern "C" hipError_t mt_launch_refs_positions(const mt_gstate* g, const uint32_
     hipLaunchKernelGGL(mt_refs_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *g, docs, handles, n, n_docs, out);
     return hipGetLastError();
 }
+
+// mt_refs_insert_local, after the resolve: one thread per record lowers it to MT_OP_INSERT_AT at its
+// reference's leaf (ordinal, getOffset) and answers the reference's local position.  The record of a
+// detached reference or of a handle that names none becomes a message without an op at the
+// document's own window (seq = currentSeq, msn = minSeq): it applies as nothing at all.
+__global__ void mt_refs_stamp_kernel(mt_gstate g, const uint32_t* __restrict__ docs, const mt_ref_pos* __restrict__ at,
+                                     mt_op_rec* __restrict__ ops, uint32_t n, uint32_t n_docs,
+                                     int32_t* __restrict__ positions) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n) return;
+    const uint32_t d = docs[w];
+    const mt_ref_pos r = at[w];
+    mt_op_rec o = ops[w];
+    if (d < n_docs && r.ordinal >= 0 && r.position >= 0) {
+        o.type = MT_OP_INSERT_AT;
+        o.pos1 = r.ordinal;
+        o.pos2 = (int32_t)r.offset;
+        positions[w] = r.position;
+    } else {
+        const mt_doc_scalars& sc = g.sc[d < n_docs ? d : 0];
+        o.seq = sc.cur_seq;
+        o.ref_seq = sc.cur_seq;
+        o.msn = sc.min_seq;
+        o.type = MT_OP_NOOP;
+        o.flags = 0;
+        o.pos1 = o.pos2 = 0;
+        o.payload_len = 0;
+        positions[w] = r.ordinal == MT_REF_BAD_HANDLE ? MT_REF_BAD_HANDLE : -1;
+    }
+    ops[w] = o;
+}
+
+extern "C" hipError_t mt_launch_refs_stamp(const mt_gstate* g, const uint32_t* docs, const mt_ref_pos* at, mt_op_rec* ops,
+                                           uint32_t n, uint32_t n_docs, int32_t* positions, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mt_refs_stamp_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *g, docs, at, ops, n, n_docs,
+                       positions);
+    return hipGetLastError();
+}

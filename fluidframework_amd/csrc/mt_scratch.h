@@ -6,7 +6,7 @@
 // A wrapper reads: argument check, layout, chain, return.  Nothing is pooled or cached: every call
 // allocates its scratch and frees it.
 //
-// With MT_SCRATCH_LAYOUT_ONLY defined only the first piece (and the two host helpers next to it) is
+// With MT_SCRATCH_LAYOUT_ONLY defined only the first piece (and the host helpers next to it) is
 // declared, and no HIP header is needed (tests/test_scratch_layout_host.py).
 #pragma once
 #include <stddef.h>
@@ -53,6 +53,26 @@ bool mt_docs_below(const T* q, uint32_t n, uint32_t n_docs) {
 inline bool mt_docs_below(const uint32_t* docs, uint32_t n, uint32_t n_docs) {
     for (uint32_t i = 0; i < n; i++)
         if (docs[i] >= n_docs) return false;
+    return true;
+}
+
+// The batch of mt_refs_insert_local (include/mtgpu.h): every document known and the documents strictly
+// ascending (one insert per document), every record a local INSERT (seq -1, type 0) whose payload
+// lies inside payload_bytes.  true: rows[0 .. n_docs] is the batch's row pointer -- record i is row i,
+// its document's only one.  false: refused, rows is not to be used.
+template <class At, class Op>
+bool mt_ref_insert_rows(const At* at, const Op* ops, uint32_t n, uint32_t n_docs, uint64_t payload_bytes, uint32_t* rows) {
+    for (uint32_t i = 0; i < n; i++) {
+        if (at[i].doc >= n_docs || (i && at[i].doc <= at[i - 1].doc)) return false;
+        if (ops[i].seq != -1 || ops[i].type != 0) return false;
+        if ((uint64_t)ops[i].payload_off + ops[i].payload_len > payload_bytes) return false;
+    }
+    uint32_t i = 0;
+    rows[0] = 0;
+    for (uint32_t d = 0; d < n_docs; d++) {
+        if (i < n && at[i].doc == d) i++;
+        rows[d + 1] = i;
+    }
     return true;
 }
 

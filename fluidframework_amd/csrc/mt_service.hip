@@ -296,7 +296,7 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 // An editing client's local edits (seq -1) touch no window; its acks assert only in
                 // updateSeqNumbers (client.ts:804-806, 821-828)
                 if (!win || ty == MT_OP_LOAD) continue;  // snapshot body append: no window update
-                if (ty > MT_OP_LOAD) {
+                if (ty > MT_OP_LOAD && !(ty == MT_OP_INSERT_AT && o.seq == -1)) {
                     win = false;
                     continue;
                 }

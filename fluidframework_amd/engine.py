@@ -120,7 +120,8 @@ def lib():
         L.mt_set_label_keys.argtypes = [vp, u32, i32, i32]
         for name, at in (('mt_refs_enable', [vp, u32]), ('mt_refs_add', [vp, vp, u32, vp]),
                          ('mt_refs_remove', [vp, vp, vp, u32]), ('mt_refs_positions', [vp, vp, vp, u32, vp]),
-                         ('mt_refs_positions_device', [vp, vp, vp, u32, vp]), ('mt_refs_dropped', [vp, vp, u32])):
+                         ('mt_refs_positions_device', [vp, vp, vp, u32, vp]), ('mt_refs_dropped', [vp, vp, u32]),
+                         ('mt_refs_insert_local', [vp, vp, vp, u32, vp, u64, vp])):
             getattr(L, name).argtypes = at
             getattr(L, name).restype = ctypes.c_int
         for name, at in (('mt_intervals_enable', [vp, u32]), ('mt_intervals_add', [vp, vp, u32, vp]),
@@ -443,6 +444,29 @@ class MergeEngine:
         assert len(d) == len(h)
         out = np.zeros(len(d), dtype=REF_POS_DTYPE)
         _check(lib().mt_refs_positions(self.h, _ptr(d), _ptr(h), len(d), _ptr(out)), 'mt_refs_positions')
+        return out
+
+    def insert_at_refs(self, docs, handles, segments):
+        """Client.insertAtReferencePositionLocal per entry (mt_refs_insert_local): `docs` strictly
+        ascending, one insert per document; `segments` per entry (client, text, props | None, flags)
+        as oplog.encode_record takes them (a Marker: oplog.F_MARKER, its refType the one character).
+        Returns per entry the pos1 of the insert op the host sends, refs.DETACHED for a detached
+        reference or refs.REF_BAD_HANDLE: for these nothing was applied."""
+        from .oplog import INSERT, encode_record
+        from .refs import REF_INSERT_DTYPE
+        at = np.zeros(len(docs), dtype=REF_INSERT_DTYPE)
+        at['doc'], at['handle'] = docs, handles
+        assert len(segments) == len(at)
+        ops = np.zeros(len(at), dtype=OP_DTYPE)
+        payload = bytearray()
+        for i, (client, text, props, flags) in enumerate(segments):
+            t, fl, data = encode_record(INSERT, flags, text, props)
+            ops[i] = (-1, 0, 0, client, t, fl, 0, 0, len(payload), len(data))
+            payload += data
+        pay = np.frombuffer(bytes(payload), dtype=np.uint8)
+        out = np.zeros(len(at), dtype=np.int32)
+        _check(lib().mt_refs_insert_local(self.h, _ptr(at), _ptr(ops), len(at), _ptr(pay), len(pay), _ptr(out)),
+               'mt_refs_insert_local')
         return out
 
     def refs_dropped(self):

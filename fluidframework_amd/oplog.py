@@ -16,6 +16,7 @@ OP_DTYPE = np.dtype([
 assert OP_DTYPE.itemsize == 32
 
 INSERT, REMOVE, ANNOTATE, NOOP = 0, 1, 2, 3
+INSERT_AT = 5           # MT_OP_INSERT_AT: a local insert at a reference's leaf (pos1 ordinal, pos2 offset)
 F_REWRITE, F_PROPS, F_GROUP_MORE = 1, 2, 4
 F_MARKER = 128          # insert of a Marker: the one text byte is its ReferenceType (ops.ts:6-16)
 NPAIRS_SHIFT = 3        # bits 3..6: property pairs in the payload, mod 16

@@ -11,7 +11,9 @@ import numpy as np
 REF_ADD_DTYPE = np.dtype([('doc', '<u4'), ('pos', '<i4'), ('ref_type', '<u4')])
 # mt_ref_pos: toPosition() (-1 detached), the segment's leaf ordinal (-1 detached), getOffset()
 REF_POS_DTYPE = np.dtype([('position', '<i4'), ('ordinal', '<i4'), ('offset', '<u4')])
-assert REF_ADD_DTYPE.itemsize == 12 and REF_POS_DTYPE.itemsize == 12
+# mt_ref_insert: the document and reference of one insertAtReferencePositionLocal
+REF_INSERT_DTYPE = np.dtype([('doc', '<u4'), ('handle', '<u4')])
+assert REF_ADD_DTYPE.itemsize == 12 and REF_POS_DTYPE.itemsize == 12 and REF_INSERT_DTYPE.itemsize == 8
 
 REF_SIMPLE = 0x0            # ReferenceType.Simple (ops.ts:7)
 REF_SLIDE_ON_REMOVE = 0x40  # ReferenceType.SlideOnRemove (ops.ts:13)

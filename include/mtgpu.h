@@ -31,13 +31,16 @@ enum mt_op_type {
     MT_OP_REMOVE = 1,   /* MergeTreeDeltaType.REMOVE                (client.ts:320-351)      */
     MT_OP_ANNOTATE = 2, /* MergeTreeDeltaType.ANNOTATE              (client.ts:358-386)      */
     MT_OP_NOOP = 3,     /* non-op message: only updateSeqNumbers(msn, seq) (client.ts:818)  */
-    MT_OP_LOAD = 4      /* snapshot body segment: MergeTree.insertSegments(pos1, [seg], ref_seq,
+    MT_OP_LOAD = 4,     /* snapshot body segment: MergeTree.insertSegments(pos1, [seg], ref_seq,
                            client, seq) as SnapshotLoader.loadBody appends it (snapshotLoader.ts:
                            192-224) -- no collab-window asserts, no updateSeqNumbers.  The segment
                            may arrive removed: pos2 = its removedSeq (-1: not removed) and the
                            high byte of `client` the low byte of its removedClient; `msn` holds the
                            high bytes of both short ids (client's in bits 0..7, removedClient's in
                            8..15: 0 below 256).  See mt_docs_load. */
+    MT_OP_INSERT_AT = 5 /* an editing client's insertAtReferencePositionLocal, lowered: pos1 = the
+                           ordinal of the reference's leaf, pos2 = the offset in it; only with seq =
+                           MT_SEQ_LOCAL.  See "local references" (mt_refs_insert_local). */
 };
 enum mt_op_flags {
     MT_F_REWRITE = 1u << 0,    /* annotate with combiningOp {name:"rewrite"} (properties.ts:118-124) */
@@ -670,8 +673,8 @@ mt_status mt_events_drain(mt_engine* eng, mt_event* out, uint64_t cap, uint32_t*
  * an append onto it then shifts by the segment's length: from a document's first dropped collection
  * on its references may differ from the reference's).  One difference is kept: where a slide left refsByOffset[offset] without an
  * `at` list the reference's addLocalRef throws (:212-219); mt_refs_add adds the reference.
- * The fold is lazy: it runs at the start of mt_refs_add / mt_refs_remove / mt_refs_positions and of
- * mt_events_drain, never inside an apply.  A document that halts keeps its references as of the
+ * The fold is lazy: it runs at the start of mt_refs_add / mt_refs_remove / mt_refs_positions /
+ * mt_refs_insert_local and of mt_events_drain, never inside an apply.  A document that halts keeps its references as of the
  * events it recorded.  mt_docs_init and mt_docs_load free the documents' references.
  * The slide target is known only to the apply: for a document that holds references the first
  * record of each REMOVE callback carries it in mt_event.pad2 (0 for every other document):
@@ -712,6 +715,37 @@ mt_status mt_refs_positions(mt_engine* eng, const uint32_t* docs, const uint32_t
 /* the same with device-resident arguments and results (asynchronous on the engine's stream) */
 mt_status mt_refs_positions_device(mt_engine* eng, const uint32_t* d_docs, const uint32_t* d_handles, uint32_t n,
                                    mt_ref_pos* d_out);
+
+/* Client.insertAtReferencePositionLocal(refPos, segment) (client.ts:216-247 ->
+ * MergeTree.insertAtReferencePosition, mergeTree.ts:2000-2097) of editing clients, one per document:
+ * the segment goes in at the reference's own leaf, not where a walk from the root for the
+ * reference's position would put it (the leaf is split at the reference's offset unless the offset
+ * or the leaf's local length is 0; the run of leaves without local length in front of it is passed
+ * as far as its farthest leaf that is not removed or whose removal is pending; the segment is linked
+ * at that leaf's index in that leaf's block).  ops[i] is a local INSERT record (seq = MT_SEQ_LOCAL,
+ * type MT_OP_INSERT, narrow; text or MT_F_MARKER, MT_F_PROPS and pairs as usual) whose pos1 / pos2
+ * are ignored, at[i] its document and reference; the documents strictly ascending (a second insert
+ * of a document could name a reference the first one's split moved, and the fold is lazy).
+ * Everything runs on the engine's stream behind the work already queued: the fold, the resolve of
+ * each reference, a kernel that lowers the device copy of each record to MT_OP_INSERT_AT (below),
+ * and the apply of the batch, as mt_submit would.  positions[i] = referencePositionToLocalPosition
+ * before the insert -- the pos1 of the insert op the host sends; the sequenced echo is an ordinary
+ * INSERT of the editing client, its ack -- or -1 for a detached reference (the reference returns
+ * undefined, client.ts:222-224), or MT_REF_BAD_HANDLE; for these two nothing is applied: no
+ * localSeq step, no pending group, no event.  MT_ERR_ARG (nothing applied): references not
+ * enabled, n > 0 with a NULL pointer, documents unknown or not ascending, a record of another kind,
+ * a payload out of bounds.
+ * The lowered form, MT_OP_INSERT_AT with seq = MT_SEQ_LOCAL, may also come through mt_submit /
+ * mt_batch_upload / ticks: pos1 = the ordinal of a linked leaf as of the moment the record is
+ * applied, pos2 = an offset below that leaf's length (else MT_DERR_BAD_OP); payload and flags those of
+ * a local INSERT.  With any other seq, or on a form that is not an editing form, the record is
+ * malformed (MT_DERR_BAD_OP).  References that carry tile or range labels are not supported. */
+typedef struct mt_ref_insert {  /* 8 bytes */
+    uint32_t doc;
+    uint32_t handle;
+} mt_ref_insert;
+mt_status mt_refs_insert_local(mt_engine* eng, const mt_ref_insert* at, const mt_op_rec* ops, uint32_t n,
+                               const uint8_t* payload, uint64_t payload_bytes, int32_t* positions);
 
 /* out[d] = collections without references that document d's table had no room to keep (see above)
  * since its references were last freed, for documents 0..n_docs-1; folds first.  0: every answer of

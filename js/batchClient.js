@@ -876,6 +876,47 @@ class BatchClient {
         ref.handle = h;
         ref._at = undefined;
     }
+    /**
+     * Client.insertAtReferencePositionLocal (client.ts:216-247): the segment (a string, {text, props} or
+     * {marker: {refType}, props}) goes in at the reference's own leaf on the device (mt_refs_insert_local:
+     * the resolve and the apply are one call, after everything queued).  Returns the insert op to send,
+     * {type: 0, pos1, seg}, or undefined for a detached reference or an empty segment.  The edit is pending
+     * as insertSegmentLocal's is: its ack, its delta callback (opArgs without a sequencedMessage) and
+     * regeneratePendingOp need nothing more.
+     */
+    insertAtReferencePositionLocal(lref, seg) {
+        if (this.longClientId === undefined) throw new Error("BatchClient: startOrUpdateCollaboration first");
+        if (lref.handle === undefined) return undefined;  // never added, or removed: no segment
+        const op = { type: INSERT, pos1: 0, seg };
+        const msg = { sequenceNumber: -1, referenceSequenceNumber: this.currentSeq, minimumSequenceNumber: 0 };
+        const r = this._record(msg, op, this._shortId(this.longClientId), false);
+        if (r.type === NOOP) return undefined;
+        if ((r.type & OP_WIDE) || r.client >= NARROW_CLIENTS) {
+            throw new Error("BatchClient: an editing client's document stays within the narrow limits (include/mtgpu.h)");
+        }
+        this.engine._enableRefs();
+        this.engine.flush();
+        this._checkError();
+        const at = Buffer.alloc(8), rec = Buffer.alloc(REC);
+        at.writeUInt32LE(this.doc, 0);
+        at.writeUInt32LE(lref.handle, 4);
+        rec.writeInt32LE(-1, 0);
+        rec.writeUInt16LE(r.client, 12);
+        rec.writeUInt8(r.type, 14);
+        rec.writeUInt8(r.flags | ((r.npairs & 15) << 3), 15);
+        rec.writeUInt32LE(r.payload.length, 28);
+        if (this.engine.recording) this.expect.push({ op });
+        this.engine.gen++;
+        const pos = native.refsInsertLocal(this.engine.handle, at, rec, r.payload.length ? r.payload : Buffer.alloc(1)).readInt32LE(0);
+        if (pos < 0) {  // detached (or a handle the device no longer knows): nothing was applied
+            if (this.engine.recording) this.expect.pop();
+            return undefined;
+        }
+        op.pos1 = pos;
+        this.engine._dispatch();
+        this._checkError();
+        return op;
+    }
     /** Client.removeLocalReference (client.ts:298-300) */
     removeLocalReference(lref) {
         if (lref.handle === undefined) return;

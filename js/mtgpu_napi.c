@@ -626,6 +626,32 @@ static napi_value refs_by_handle(napi_env env, napi_callback_info info, int posi
 static napi_value refs_remove(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 0); }
 static napi_value refs_positions(napi_env env, napi_callback_info info) { return refs_by_handle(env, info, 1); }
 
+/* refsInsertLocal(engine, at (8-byte mt_ref_insert rows), ops (32-byte records), payload) -> Buffer of
+ * i32 positions (mt_refs_insert_local) */
+static napi_value refs_insert_local(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4], out;
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    engine_box* b = argc == 4 ? get_box(env, argv[0]) : NULL;
+    size_t na = 0, no = 0, np = 0;
+    const void* at = b ? buffer_data(env, argv[1], &na) : NULL;
+    const void* ops = b ? buffer_data(env, argv[2], &no) : NULL;
+    const void* pay = b ? buffer_data(env, argv[3], &np) : NULL;
+    if (!b || na % sizeof(mt_ref_insert) || no % sizeof(mt_op_rec) || na / sizeof(mt_ref_insert) != no / sizeof(mt_op_rec)) {
+        napi_throw_type_error(env, NULL, "refsInsertLocal(engine, at, ops, payload)");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(na / sizeof(mt_ref_insert));
+    void* data = NULL;
+    NAPI_CALL(env, napi_create_buffer(env, n ? n * sizeof(int32_t) : 1, &data, &out));
+    enter(b);
+    mt_status st = mt_refs_insert_local(b->e, (const mt_ref_insert*)at, (const mt_op_rec*)ops, n, (const uint8_t*)pay, np,
+                                        (int32_t*)data);
+    leave(b);
+    if (st) return throw_status(env, "mt_refs_insert_local", st);
+    return out;
+}
+
 /* intervalsEnable(engine, perDoc): room for intervals (mt_intervals_enable; after refsEnable) */
 static napi_value intervals_enable(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -922,6 +948,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"refsAdd", NULL, refs_add, NULL, NULL, NULL, napi_default, NULL},
         {"refsRemove", NULL, refs_remove, NULL, NULL, NULL, napi_default, NULL},
         {"refsPositions", NULL, refs_positions, NULL, NULL, NULL, napi_default, NULL},
+        {"refsInsertLocal", NULL, refs_insert_local, NULL, NULL, NULL, napi_default, NULL},
         {"intervalsEnable", NULL, intervals_enable, NULL, NULL, NULL, napi_default, NULL},
         {"intervalsAdd", NULL, intervals_add, NULL, NULL, NULL, napi_default, NULL},
         {"intervalsRemove", NULL, intervals_remove, NULL, NULL, NULL, napi_default, NULL},

@@ -6,6 +6,8 @@
 // A record with marker-relative ends (type bits 3 / 4, include/mtgpu.h) becomes an op with relativePos1 /
 // relativePos2 {id, before, offset?} in place of pos1 / pos2: with opts.markerKey = k, key k is the
 // reserved "markerId" property and its value id v the id "m<v>".
+// A local record of type 5 (MT_OP_INSERT_AT) in a fixture log names a reference of the fixture in pos1:
+// it becomes an insert op {type: 0, refId, seg} without a position.
 const fs = require("fs");
 
 function loadLog(file) {
@@ -93,6 +95,12 @@ function absOp(log, r, opts) {
     if (type === 0) {
         const text = textOf(log, r);
         return { type: 0, pos1: r.pos1, seg: (r.flags & 2) ? { text, props: propsOf(log, r, opts) } : text };
+    }
+    if (type === 5) {  // MT_OP_INSERT_AT of a fixture: an insertAtReferencePositionLocal at reference `refId`
+        const op = absOp(log, Object.assign({}, r, { type: r.type & ~0x07 }), opts);
+        delete op.pos1;
+        op.refId = r.pos1;
+        return op;
     }
     if (type === 1) return { type: 1, pos1: r.pos1, pos2: r.pos2 };
     if (type === 2) {
