@@ -10,40 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import WIDE_SETS, load_golden
+from view_docs import expected as _expected, high_members, units as _units, view_len as _view_len
 
 pytestmark = pytest.mark.gpu
-
-
-def _units(text):
-    """cachedLength: UTF-16 code units (textSegment.ts:45); a marker is 1"""
-    return 1 if isinstance(text, dict) else len(text.encode('utf-16-le', 'surrogatepass')) // 2
-
-
-def _view_len(seg, ref_seq, client):
-    """nodeLength's leaf branch (mergeTree.ts:1659-1697) over a canonical segment row; ref_seq None:
-    the local view."""
-    text, seq, cl, rseq, rcl, ovl = seg[0], seg[1], seg[2], seg[3], seg[4], seg[5]
-    ln = _units(text)
-    removed = rcl != -1 or rseq != -1
-    if ref_seq is None:
-        return 0 if removed else ln
-    if not (cl == client or (seq != -1 and seq <= ref_seq)):
-        return 0
-    if removed and (rcl == client or client in ovl or (rseq != -1 and rseq <= ref_seq)):
-        return 0
-    return ln
-
-
-def _expected(state, pos, ref_seq, client):
-    segs = state['segs']
-    left = pos
-    for i, s in enumerate(segs):
-        vl = _view_len(s, ref_seq, client)
-        if left < vl:
-            lpos = sum(_view_len(x, None, 0) for x in segs[:i])
-            return i, left, lpos, _units(s[0])
-        left -= vl
-    return -1, left, sum(_view_len(x, None, 0) for x in segs), 0
 
 
 @pytest.mark.parametrize('name', ['scenarios', 'markers', 'synth_c3', 'synth_c4', 'synth_tiny'] + WIDE_SETS)
@@ -53,12 +22,20 @@ def test_resolve_positions_match_reference_states(name):
     eng = MergeEngine(batch.n_docs, ops_per_launch=32)
     eng.apply(batch)
     rows, want = [], []
+    high_views = 0
     for r in exp:
         d, st = r['doc'], r['state']
         if eng.error(d) != (0, 0):
             continue
-        clients = sorted({s[2] for s in st['segs'] if s[2] > 0})[:3]
-        views = [(None, 0)] + [(rs, c) for c in clients for rs in (st['msn'], st['seq'])]
+        inserters = sorted({s[2] for s in st['segs'] if s[2] > 0})
+        clients = inserters[:3]
+        # and where the state has them: the highest inserter, a removedClient and up to three overlap
+        # members >= 64 (in a wide document these read the overlap list and the ids' high bytes)
+        removed = [s for s in st['segs'] if s[4] > 0]
+        extra = inserters[-1:] + [s[4] for s in removed[:1]] + sorted({m for s in removed for m in high_members(s[5])})[-3:]
+        extra = [c for c in dict.fromkeys(extra) if c not in clients]
+        high_views += sum(1 for c in extra if c >= 64)
+        views = [(None, 0)] + [(rs, c) for c in clients + extra for rs in (st['msn'], st['seq'])]
         for ref_seq, client in views:
             vlen = sum(_view_len(s, ref_seq, client) for s in st['segs'])
             stride = max(1, (vlen + 2) // 24)
@@ -73,6 +50,14 @@ def test_resolve_positions_match_reference_states(name):
             lp += _view_len(s, None, 0)
         rows.append((d, n, POS_LOCAL, 0, POS_OF_ORDINAL))
         want.append((-1, None, None, None))
+        for c in extra:   # getPosition is the local view's whoever asks
+            lp = 0
+            for i, s in enumerate(st['segs']):
+                rows.append((d, i, st['seq'], c, POS_OF_ORDINAL))
+                want.append((i, 0, lp, _units(s[0])))
+                lp += _view_len(s, None, 0)
+            rows.append((d, n, st['msn'], c, POS_OF_ORDINAL))
+            want.append((-1, None, None, None))
     q = np.array(rows, dtype=POS_QUERY_DTYPE)
     got = eng.resolve_positions(q)
     for k, (g, w) in enumerate(zip(got, want)):
@@ -85,6 +70,7 @@ def test_resolve_positions_match_reference_states(name):
         if not ok:
             pytest.fail(f'{name}: query {rows[k]} -> {tuple(int(x) for x in g)}, reference state gives {w}')
     assert len(rows) > 100
+    assert high_views > 0 or name not in WIDE_SETS
 
 
 def test_resolve_positions_on_editing_documents():
