@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, 'libmtgpu.so')
 SOURCES = ['mt_apply.hip', 'mt_apply_reg.hip', 'mt_service.hip', 'mt_refs.hip', 'mt_intervals.hip', 'mt_text.hip', 'mt_markers.hip', 'mt_deli.hip', 'mt_engine.cpp',
            'mt_queries.cpp', 'mt_readout.cpp', 'mt_comm.cpp']
 HEADERS = ['mt_state.h', 'mt_wave.h', 'mt_checksum.h', 'mt_synth.h', 'mt_seqwin.h', 'mt_view.h', 'mt_marker.h', 'mt_launch.h',
-           'mt_engine_impl.h', 'mt_scratch.h', '../../include/mtgpu.h']
+           'mt_engine_impl.h', 'mt_scratch.h', 'mt_reg_lds.h', '../../include/mtgpu.h']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = os.environ.get('PYTORCH_ROCM_ARCH', 'gfx950')
 

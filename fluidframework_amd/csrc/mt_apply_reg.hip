@@ -33,12 +33,12 @@
 #include "../../include/mtgpu.h"
 #include "mt_seqwin.h"
 #include "mt_launch.h"
+#include "mt_reg_lds.h"  // RLds<K>, kMaxNodes
 #include "mt_state.h"
 #include "mt_wave.h"
 
 namespace mtr {
 
-constexpr int kMaxNodes = 8;           // MaxNodesInBlock, mergeTree.ts:334
 constexpr int kTextGranularity = 256;  // MergeTree.TextSegmentGranularity, mergeTree.ts:1059
 constexpr int kNarrowClients = 32;     // register overlap set: clients 1..32 at bit C-1 of ov
 constexpr int kC64Clients = 63;        // ... and 33..63 at bit C-33 of oh (the C64 instantiation)
@@ -130,42 +130,6 @@ MT_DEV uint64_t prof_now() {
 #define PROF_CNT(slot, v)
 #endif
 
-template <int K>
-struct RLds {
-    static constexpr int CAP = 64 * K;
-    // leaf blocks, blocks per interior level, heap entries (1-based): the class limits of mt::Lds at
-    // CAP, and at least those of the 256 class -- the launch's worst-case growth (mt_bin_kernel: 2 leaf
-    // blocks, 1 interior block and 4 heap entries per op) needs them for a b = 32 launch to fit the
-    // 192 class at all (mt_engine.cpp kClassParams)
-    static constexpr int LB = CAP / 2 > 128 ? CAP / 2 : 128;
-    static constexpr int IB = CAP / 8 + 8 > 40 ? CAP / 8 + 8 : 40;
-    static constexpr int H = CAP / 2 + 64 > 192 ? CAP / 2 + 64 : 192;
-    uint64_t props[CAP];    // by segment id: 8 keys x u8 value id
-    // scr: scratch by slot / position / leaf block (load, store); tln: by segment id, the text length
-    // while linked, 0 once unlinked (the op loop's compaction).  They share their words, as neither
-    // is live while the other is (load writes tln after its last scr read; store runs after the op
-    // loop): 4 B per slot less LDS, which lifts the waves per CU that LDS allows at K = 7, 9, 10
-    // and 14-16 to what the registers allow (K = 9: 11 -> 12, K = 10: 11 -> 12)
-    union {
-        int32_t scr[CAP + 1];
-        uint32_t tln[CAP + 1];
-    };
-    int32_t hseq[H];
-    uint16_t toff[CAP];     // by segment id: text view offset (at store: id -> position)
-    uint16_t hslot[H];      // heap entry -> segment id
-    uint8_t ibcnt[MT_MAXLEV - 1][IB];  // interior levels: level L's child counts in ibcnt[L - 1]
-    uint8_t lbsc[LB + 1];   // store staging: needsScour per leaf block
-    int32_t nb[MT_MAXLEV];  // blocks per interior level (leaf blocks are counted by BS bits)
-    // scour scratch: the live children by rank, one array per field (separate 4-byte stores: no
-    // 4-register tuple built per slot, which cost ~20 VGPRs at the scour's register peak)
-    // zr[q]: the removal seq of a removed child q, else its seq; zr[8 + q] its li, zr[16 + q] its cf,
-    // zr[24 + q] its slot
-    uint32_t zr[4 * kMaxNodes];
-    // the lanes' discard words of the branch-free LDS stores (a lane with nothing to store writes
-    // here; never read)
-    uint64_t dum[64];
-};
-
 struct Elem {
     uint32_t sw;  // seq | rseq as window offsets (mt_seqwin.h); the exact seq in the classes that keep rsq
     uint32_t rsq;  // (those classes) the exact rseq
@@ -234,6 +198,17 @@ struct RWave {
     MT_DEV uint8_t* arena() const { return abase + (size_t)text_half * textcap; }
 
     MT_DEV int idx(int j) const { return lane * K + j; }
+    // the per-id text lengths in the class's width, and the store's staging words: the class's own (on
+    // tln's words), or props' (RLds::SCR_OWN)
+    using TL = typename L::tln_t;
+    MT_DEV TL* tln() const {
+        if constexpr (L::SCR_OWN) return s.tln32;
+        else return s.tln16;
+    }
+    MT_DEV int32_t* scr() const {
+        if constexpr (L::SCR_OWN) return s.scr_own;
+        else return s.scr_props;
+    }
 
     MT_DEV void fail(int code, int32_t sq) {
         if (err == 0) {
@@ -727,9 +702,10 @@ struct RWave {
         const uint8_t* src0 = arena();
         uint8_t* dst = abase + (size_t)(text_half ^ 1u) * textcap;
         uint32_t carry = 0;
+        const int big = L::SCR_OWN ? -1 : uni(s.big);
         for (int base = 0; base < nid; base += 64) {
             const int i = base + lane;
-            const uint32_t l = i < nid ? s.tln[i] : 0u;
+            const uint32_t l = i < nid ? (i == big ? 65536u : (uint32_t)tln()[i]) : 0u;
             const uint32_t incl = (uint32_t)wave_incl_scan((int)l);
             const uint32_t at = carry + incl - l;
             if (l) {
@@ -795,8 +771,9 @@ struct RWave {
         if (lane == 0) {
             s.props[t] = pid;
             s.toff[t] = (uint16_t)(to + (uint32_t)off);
-            s.tln[id] = (uint32_t)off;
-            s.tln[t] = len - (uint32_t)off;
+            tln()[id] = (TL)off;
+            tln()[t] = (TL)(len - (uint32_t)off);
+            if (!L::SCR_OWN && (len >> 16)) s.big = -1;
         }
         c.lli = (uint32_t)off | (id << kLenBits);
         // the left part ends in "\n" only if the segment has one: otherwise known now (F_NLQ: the
@@ -961,7 +938,10 @@ struct RWave {
             text_top = top + total;
             wave_sync();
         }
-        if (lane == 0) s.tln[pid_] = total;
+        if (lane == 0) {
+            tln()[pid_] = (TL)total;
+            if (!L::SCR_OWN && (total >> 16)) s.big = (int32_t)pid_;
+        }
         const uint32_t pcf = (uint32_t)__builtin_amdgcn_readlane((int)vcf, p);
         const uint32_t lcf = (uint32_t)__builtin_amdgcn_readlane((int)vcf, (int)lastq);
         const uint32_t anynl = __ballot(in_run && (vcf & F_HASNL)) ? F_HASNL : 0u;
@@ -1109,7 +1089,10 @@ struct RWave {
         }
         // unlink: the slots become dead in place (their block marks stay)
         const bool gone = mine && ((unlink >> lane) & 1u);
-        if (gone) s.tln[id_of(vli)] = 0u;
+        if (gone) {
+            tln()[id_of(vli)] = 0;
+            if (!L::SCR_OWN && (ql >> 16)) s.big = -1;
+        }
         uint64_t gm = __ballot(gone);
         uint32_t kill = 0;
         while (gm) {
@@ -1330,7 +1313,8 @@ struct RWave {
         if (lane == 0) {
             s.props[t] = p;
             s.toff[t] = (uint16_t)top;
-            s.tln[t] = (uint32_t)tlen;
+            tln()[t] = (TL)tlen;
+            if (!L::SCR_OWN && (tlen >> 16)) s.big = t;
         }
         text_top = top + (uint32_t)tlen;
         wave_sync();
@@ -1742,8 +1726,9 @@ struct RWave {
         for (int j = 0; j < K; j++) {
             s.props[i0 + j] = (uint64_t)pw[2 * j] | ((uint64_t)pw[2 * j + 1] << 32);
             s.toff[i0 + j] = (uint16_t)vto[j];
-            s.scr[i0 + j] = 0;
+            tln()[i0 + j] = 0;
         }
+        if (lane == 0) s.big = -1;
 #pragma unroll
         for (int c = 0; c < HC; c++) {
             const int i = 1 + c * 64 + lane;
@@ -1779,7 +1764,7 @@ struct RWave {
                     const int c = b < nb0 ? (int)lbc_[cc] : 0;
                     const int scv = (int)lbs_[cc];
                     const int incl = wave_incl_scan(c) + carry;
-                    if (b < nb0 && c > 0) s.scr[incl - c] = 1 | (scv << 1);
+                    if (b < nb0 && c > 0) tln()[incl - c] = (TL)(1 | (scv << 1));
                     nempty += __popcll(wave_ballot(b < nb0 && c == 0));
                     carry = wave_last(incl);
                 }
@@ -1793,7 +1778,7 @@ struct RWave {
         for (int j = 0; j < K; j++) {
             const bool in = i0 + j < n;
             const bool rmj = (byte_at(bfw, j) & MT_SF_REMOVED) != 0;
-            const int mk = s.scr[i0 + j];  // scr[i] for i >= n is harmless (selected away)
+            const int mk = tln()[i0 + j];  // (the marks; for i >= n harmless: selected away)
             const uint32_t ds = mt_sw_off((int32_t)vsq[j], base_seq);
             const uint32_t dr = rmj ? mt_sw_off((int32_t)vrs[j], base_seq) : 0u;
             if constexpr (PK) {
@@ -1825,9 +1810,12 @@ struct RWave {
             }
             return false;
         }
-        wave_sync();  // (tln shares scr's words: the marks are read)
+        wave_sync();  // (the marks are read: tln takes the lengths)
 #pragma unroll
-        for (int j = 0; j < K; j++) s.tln[i0 + j] = vln[j];
+        for (int j = 0; j < K; j++) {
+            tln()[i0 + j] = (TL)vln[j];
+            if (!L::SCR_OWN && i0 + j < n && (vln[j] >> 16)) s.big = i0 + j;
+        }
         // empty leaf blocks (rare): a dead slot holds each one's place and marks
         if (nempty) {
             if (ns + nempty > CAP) {
@@ -1870,14 +1858,14 @@ struct RWave {
         int32_t* const dum = reinterpret_cast<int32_t*>(s.dum) + lane;
 #pragma unroll
         for (int j = 0; j < K; j++)
-            *(((lb >> j) & 1u) ? &s.scr[pbase + __popc(lb & ((1u << j) - 1u))] : dum) = (int32_t)v[j];
+            *(((lb >> j) & 1u) ? &scr()[pbase + __popc(lb & ((1u << j) - 1u))] : dum) = (int32_t)v[j];
         wave_sync();
         // four rows per LDS round trip (scr holds CAP + 1 entries: the reads past nn are clamped)
 #pragma clang loop unroll(disable) vectorize(disable)
         for (int base = 0; base < nn; base += 256) {
             uint32_t v[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) v[q] = (uint32_t)s.scr[min(base + 64 * q + lane, CAP)];
+            for (int q = 0; q < 4; q++) v[q] = (uint32_t)scr()[min(base + 64 * q + lane, CAP)];
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (base + 64 * q + lane < nn) put(base + 64 * q + lane, v[q]);
@@ -1914,6 +1902,21 @@ struct RWave {
                 for (int j = 0; j < K; j++)
                     if ((q >> j) & 1u) cf[j] = (cf[j] & ~(F_NL | F_NLQ)) | (ch[j] == '\n' ? F_NL : 0u);
             }
+        }
+        // (the classes whose scr shares props' words, RLds::SCR_OWN false) the property sets, by segment
+        // id in LDS, into registers and out first
+        if constexpr (!L::SCR_OWN) {
+            VU plo, phi;
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const uint64_t p = s.props[((lb >> j) & 1u) ? id_of(li[j]) : 0u];
+                plo[j] = (uint32_t)p;
+                phi[j] = (uint32_t)(p >> 32);
+            }
+            wave_sync();
+            MT_GLOB uint32_t* const pw = reinterpret_cast<MT_GLOB uint32_t*>(gp(g.props) + so);
+            store_field(plo, lb, pbase, nn, [&](int i, uint32_t v) { pw[2 * i] = v; });
+            store_field(phi, lb, pbase, nn, [&](int i, uint32_t v) { pw[2 * i + 1] = v; });
         }
         // the exact seq / rseq (mt_seqwin.h): base_seq + offset, and for an offset of 0 the number the
         // segment's origin row held at load.  Those rows are read here, all of them before the first
@@ -1956,7 +1959,7 @@ struct RWave {
             const uint32_t id = id_of(v);
             gp(g.len)[so + i] = len_of(v);
             gp(g.toff)[so + i] = s.toff[id];
-            gp(g.props)[so + i] = s.props[id];
+            if constexpr (L::SCR_OWN) gp(g.props)[so + i] = s.props[id];
         });
         // leaf blocks: live children and needsScour, in block order
         const uint32_t bm = bs_bits();
@@ -1966,17 +1969,17 @@ struct RWave {
         for (int j = 0; j < K; j++) {
             if ((bm >> j) & 1u) {
                 const int b = bbase + __popc(bm & ((1u << j) - 1u));
-                s.scr[b] = pbase + __popc(lb & ((1u << j) - 1u));
+                scr()[b] = pbase + __popc(lb & ((1u << j) - 1u));
                 s.lbsc[b] = (uint8_t)(((sc0 >> j) & 1u) | (((sc1 >> j) & 1u) << 1));
             }
         }
-        if (lane == 0) s.scr[nb0] = nn;
+        if (lane == 0) scr()[nb0] = nn;
         wave_sync();
         const size_t lo = (size_t)d * g.lbcap;
         int nempty = 0;
 #pragma clang loop unroll(disable) vectorize(disable)
         for (int b = lane; b < nb0; b += 64) {
-            const int cnt = s.scr[b + 1] - s.scr[b];
+            const int cnt = scr()[b + 1] - scr()[b];
             gp(g.lbcnt)[lo + b] = (uint8_t)cnt;
             gp(g.lbscour)[lo + b] = s.lbsc[b];
             nempty += cnt == 0 ? 1 : 0;
@@ -2097,10 +2100,14 @@ MT_DEV KGState& kernarg_gstate() {
 // kept: K = 5 at four waves (spill-free) its C4 class 60.1 -> 65.0 ms; K = 8 at three (spill-free) its C3
 // class 43.0 -> 45.5 ms.  Replacing cum by a visibility mask and a lane base (two registers for K) was
 // measured and rejected: its consumers rebuild the prefix slot by slot, and the step ran 1.7 % slower on
-// C3 alone and 1.2 % slower on top of the packing.  Four waves at K = 9 / 10 would spill 196 / 272 B at
-// round 6's code (and RLds<10> caps a CU at 12 waves): not tried.
+// C3 alone and 1.2 % slower on top of the packing.
+// Round 10 (profiles/r10_ab/ab1_lds_k9_C3.log, profiles/r10_resource_usage_reg.txt): K = 9 at four waves takes
+// 52 B of scratch at 128 VGPRs, and RLds<9> came down from 11,624 to 10,184 B (mt_reg_lds.h), so the 16 waves
+// per CU fit its LDS too: C3's 576 class 55.8 ms on the parent, 56.2 with the new block at three waves, 50.7 at
+// four.  K = 10 at four would keep 92 B of scratch, above the ~60 B rule: it stays at three (measured all the
+// same: its class 55.5 ms on the parent, 55.8 with the new block at three waves, 54.3 at four).
 constexpr int wpe_default(int K) {
-    return K <= 3 ? 7 : K <= 5 ? 5 : K <= 8 ? 4 : K <= 12 ? 3 : 2;
+    return K <= 3 ? 7 : K <= 5 ? 5 : K <= 9 ? 4 : K <= 12 ? 3 : 2;
 }
 // MT_WPE_OV={w0,w1,...,w16} overrides classes one by one (0 = the default), for A/B builds.
 #ifndef MT_WPE_OV

@@ -33,7 +33,7 @@ def build_one(spec):
     src = os.path.join(SNAP, 'fluidframework_amd', 'csrc', 'mt_apply_reg.hip')
     subprocess.check_call([HIPCC] + FLAGS + defs.split() + ['-c', src, '-o', obj])
     others = [os.path.join(PKG, 'build', f + '.o') for f in
-              ('mt_apply.hip', 'mt_service.hip', 'mt_refs.hip', 'mt_intervals.hip', 'mt_text.hip', 'mt_deli.hip',
+              ('mt_apply.hip', 'mt_service.hip', 'mt_refs.hip', 'mt_intervals.hip', 'mt_text.hip', 'mt_markers.hip', 'mt_deli.hip',
                'mt_engine.cpp', 'mt_queries.cpp', 'mt_readout.cpp', 'mt_comm.cpp')]
     lib = os.path.join(out, f'libmtgpu_{name}.so')
     subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-shared', '-o', lib, obj] + others +

@@ -6,6 +6,7 @@ to its granule (e.g. K = 9: 226 here, 116 in profiles/r02_kernel_stats_C3_v2.csv
     python tools/resource_usage.py > profiles/r02_resource_usage_reg.txt"""
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -32,6 +33,21 @@ def main():
             return x.group(1) if x else '?'
         print('  %-8s %6s %6s %14s %10s' % (kname, g('VGPRs'), g('SGPRs'), g(r'ScratchSize \[bytes/lane\]'),
                                             g(r'Occupancy \[waves/SIMD\]')))
+    lds_sizes()
+
+
+def lds_sizes():
+    """sizeof(RLds<K>) (csrc/mt_reg_lds_sizes.cpp, a host build) and the waves per CU its LDS admits: 160 KiB
+    allocated per wave in 512-byte granules, at most the 32 wave slots of the four SIMDs"""
+    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
+    with tempfile.TemporaryDirectory() as d:
+        subprocess.run([cxx, '-std=c++17', '-o', os.path.join(d, 'rlds'),
+                        os.path.join(os.path.dirname(SRC), 'mt_reg_lds_sizes.cpp')], check=True)
+        out = subprocess.run([os.path.join(d, 'rlds')], capture_output=True, text=True, check=True).stdout
+    print('# sizeof(RLds<K>) in bytes, waves per CU by LDS (160 KiB, 512-byte granules, <= 32)')
+    for line in out.strip().split('\n'):
+        k, size = (int(x) for x in line.split())
+        print('  lds K=%-4d %6d %6d' % (k, size, min(32, (160 * 1024) // (-(-size // 512) * 512))))
 
 
 if __name__ == '__main__':
