@@ -86,8 +86,16 @@ MT_DEV LocRow loc_row(const mt_gstate& g, uint32_t d) {
 // W: a wide document (include/mtgpu.h "limits"): per slot also the overlap ids >= 64 (ovx) and the
 // property words ph / pxl / pxh / pxx (u16 value ids, keys 8..31); UTF-16 text.  GW: (LOC) group-mask
 // words per slot, 64 GW pending edits at most (GW > 1: MT_WIDE_GROUPS documents, HBM workspace only)
+// (W && LOC: the wide editing form) the pending property counts of keys 8..31 by slot (mt_state.h
+// MT_PKW_WORDS).  A base of Lds, empty in every other form: their layouts and sizes stay what they were
+template <int CAP, bool ON>
+struct LdsPkw {};
+template <int CAP>
+struct LdsPkw<CAP, true> {
+    uint64_t pkw[MT_PKW_WORDS * CAP];
+};
 template <int CAP, bool LOC = false, bool W = false, int GW = 1>
-struct Lds {
+struct Lds : LdsPkw<CAP, LOC && W> {
     static constexpr int LB = CAP / 2;      // leaf blocks
     static constexpr int IB = CAP / 8 + 8;  // blocks per interior level
     static constexpr int H = CAP / 2 + 64;  // heap entries (1-based)
@@ -212,7 +220,14 @@ struct Wave {
     uint64_t* lsqp = nullptr;  // (LOC) the localSeq pairs by slot (Lds::lsq, or HBM: mt_gstate.lsqx)
     uint64_t* pkp = nullptr;   // (LOC) the pending property counts by slot (Lds::pk, or HBM: mt_gstate.pkx)
     uint64_t* gmp = nullptr;   // (LOC) the pending-group masks by slot (Lds::gm, or HBM: mt_gstate.gmxs)
-    uint32_t* gtp = nullptr;   // (LOC) the groups' creation stamps and localSeqs (LocState, or the
+    uint64_t* pkwp = nullptr;  // (W && LOC) the pending property counts of keys 8..31 by slot (LdsPkw::pkw)
+    static constexpr bool WL = W && LOC;  // the wide editing form
+    bool ackw = false;         // (WL) the ack being applied is a wide record (3-byte pairs)
+    // (WL) the pending count of key k of a slot whose first count word is pk0
+    MT_DEV uint32_t pkc(uint64_t pk0, int sl, int k) const {
+        return k < 8 ? MT_PK_KEY(pk0, k) : MT_PK_KEY(pkwp[MT_PKW_WORDS * sl + (k >> 3) - 1], k & 7);
+    }
+    uint32_t* gtp = nullptr;  // (LOC) the groups' creation stamps and localSeqs (LocState, or the
     uint32_t* glsp = nullptr;  // document's mt_loc in HBM)
     // (LOC) their writes are read by other lanes: through HBM in the LDS-staged forms
     MT_DEV static void ct_publish() {
@@ -434,6 +449,7 @@ struct Wave {
                 ln = s.len[sl];
                 uint64_t pk = 0;  // (LOC, a remote annotate: keys with pending local changes are skipped)
                 if constexpr (LOC) pk = (S != -1 && (f & MT_SF_PDEF)) ? pkp[sl] : 0ull;
+                const bool pkon = WL && S != -1 && (f & MT_SF_PDEF);  // (WL) so do its counts of keys >= 8
                 ll = (f & MT_SF_REMOVED) ? 0 : (int)ln;
                 const int ce = s.cum[i], cs = cstart(i);
                 hit = ce > cs && cs < end && ce > start;
@@ -451,7 +467,8 @@ struct Wave {
                         if (rewrite) {
                             for (int k = 0; k < kKeys; k++) {
                                 const uint32_t old = pdef ? pval(sl, k) : 0u;
-                                if (old && (k >= 8 || MT_PK_KEY(pk, k) == 0)) {
+                                // (no local change of the key pending)
+                                if (old && (WL ? !pkon || pkc(pk, sl, k) == 0 : k >= 8 || MT_PK_KEY(pk, k) == 0)) {
                                     bool keep = false;  // a key the rewrite sets again keeps its value here
                                     for (int q = 0; q < pr.np; q++) keep = keep || (pr.key(q) == k && pr.val(q) != 0);
                                     if (!keep) pm |= 1u << k;
@@ -461,7 +478,7 @@ struct Wave {
                         }
                         for (int q = 0; q < pr.np; q++) {
                             const int k = pr.key(q);
-                            if (k < 8 && MT_PK_KEY(pk, k) > 0) continue;
+                            if (WL ? pkon && pkc(pk, sl, k) > 0 : k < 8 && MT_PK_KEY(pk, k) > 0) continue;
                             const uint32_t prev = (rewrite && pr.val(q) == 0) ? 0u : (pdef ? pval(sl, k) : 0u);
                             pm |= 1u << k;
                             pv[k] = (uint16_t)prev;
@@ -829,6 +846,8 @@ struct Wave {
             if constexpr (LOC) {  // segmentGroups.copyTo + the property manager's counts (mergeTree.ts:555-560)
                 gm_copy(t, sl);
                 pkp[t] = pkp[sl];
+                if constexpr (WL)
+                    for (int q = 0; q < MT_PKW_WORDS; q++) pkwp[MT_PKW_WORDS * t + q] = pkwp[MT_PKW_WORDS * sl + q];
                 lsqp[t] = lsqp[sl];
                 s.lc.stamp = s.lc.stamp + 1;  // stamps start at 1: segments from before editing have 0
                 ctp[t] = s.lc.stamp;
@@ -1175,6 +1194,8 @@ struct Wave {
                 gm_zero(t);
                 if (S == -1) gm_set(t, s.lc.ghi);
                 pkp[t] = 0;
+                if constexpr (WL)
+                    for (int q = 0; q < MT_PKW_WORDS; q++) pkwp[MT_PKW_WORDS * t + q] = 0ull;
                 lsqp[t] = S == -1 ? (uint64_t)s.lc.lseq : 0ull;
                 s.lc.stamp = s.lc.stamp + 1;
                 const uint32_t stamp = s.lc.stamp;
@@ -1307,6 +1328,8 @@ struct Wave {
                     gm_zero(t);
                     if (S == -1) gm_set(t, s.lc.ghi);
                     pkp[t] = 0;
+                    if constexpr (WL)
+                        for (int q = 0; q < MT_PKW_WORDS; q++) pkwp[MT_PKW_WORDS * t + q] = 0ull;
                     lsqp[t] = S == -1 ? (uint64_t)s.lc.lseq : 0ull;
                     s.lc.stamp = s.lc.stamp + 1;
                     const uint32_t stamp = s.lc.stamp;
@@ -1418,7 +1441,9 @@ struct Wave {
                         if (local) gm_set(sl, gN);
                     }
                     if (!is_remove && track()) mark_stale(sl);
-                    if (LOC && !is_remove) {
+                    if (WL && !is_remove) {
+                        annotate_loc_wide(sl, pr, rewrite, local);
+                    } else if (LOC && !is_remove) {
                         annotate_loc(sl, pr.p, pr.np, rewrite, local);
                     } else if (is_remove) {
                         bool pend_rm = false;
@@ -1539,6 +1564,44 @@ struct Wave {
         }
     }
 
+    // annotate_loc in the wide editing form: u16 value ids over keys 0..31 (pval / pset), the counts of keys
+    // >= 8 in the slot's three further words (mt_state.h MT_PKW_WORDS), the op's pairs narrow or wide.
+    // (Keys >= 16 only with the extension staged: apply_local / apply_abs refuse the op otherwise.)
+    MT_DEV void annotate_loc_wide(int sl, const Pairs& pr, bool rewrite, bool local) {
+        if constexpr (WL) {
+            const bool pdef = (s.flags[sl] & MT_SF_PDEF) != 0;
+            uint64_t pk[1 + MT_PKW_WORDS];
+            pk[0] = pdef ? pkp[sl] : 0ull;
+            for (int q = 0; q < MT_PKW_WORDS; q++) pk[1 + q] = pdef ? pkwp[MT_PKW_WORDS * sl + q] : 0ull;
+            if (!pdef) pclear(sl);
+            s.flags[sl] |= MT_SF_PDEF;
+            const bool dropped = !local && MT_PK_RW(pk[0]) > 0;  // a local rewrite is pending: blocked whole
+            if (!dropped) {
+                if (rewrite) {
+                    if (local) pk[0] += 1ull << 56;
+                    const int nk = xk_p ? MT_MAX_KEYS_WIDE : 16;
+                    for (int k = 0; k < nk; k++) {
+                        if (!pval(sl, k)) continue;
+                        bool keep = false;  // newProps[key] truthy
+                        for (int q = 0; q < pr.np; q++) keep = keep || (pr.key(q) == k && pr.val(q) != 0);
+                        if (!keep && (local || MT_PK_KEY(pk[k >> 3], k & 7) == 0)) pset(sl, k, 0u);
+                    }
+                }
+                for (int q = 0; q < pr.np; q++) {
+                    const int k = pr.key(q);
+                    if (local) {
+                        if (MT_PK_KEY(pk[k >> 3], k & 7) < 127) pk[k >> 3] += 1ull << (7 * (k & 7));
+                    } else if (MT_PK_KEY(pk[k >> 3], k & 7) > 0) {
+                        continue;
+                    }
+                    pset(sl, k, pr.val(q));
+                }
+            }
+            pkp[sl] = pk[0];
+            for (int q = 0; q < MT_PKW_WORDS; q++) pkwp[MT_PKW_WORDS * sl + q] = pk[1 + q];
+        }
+    }
+
     // ackPendingSegment (client.ts:588-625 -> mergeTree.ts:1893-1920, BaseSegment.ack :487-522): the
     // editing client's own sequenced message settles its oldest pending edit.  Its group's list
     // order (which the heap pushes follow) is rebuilt: the members that existed when the edit was
@@ -1555,6 +1618,14 @@ struct Wave {
                 } else if (type == MT_OP_REMOVE) {
                     lsqp[sl] &= 0xFFFFFFFFull;
                     if (s.rseq[sl] == -1) s.rseq[sl] = S;  // else a remote removal overwrote it
+                } else if constexpr (WL) {  // (keys 0..31: the slot's four count words; pairs narrow or wide)
+                    const Pairs pr{pairs, np, ackw};
+                    if (rewrite && MT_PK_RW(pkp[sl]) > 0) pkp[sl] -= 1ull << 56;
+                    for (int q = 0; q < np; q++) {
+                        const int key = pr.key(q);
+                        uint64_t* w = key < 8 ? &pkp[sl] : &pkwp[MT_PKW_WORDS * sl + (key >> 3) - 1];
+                        if (MT_PK_KEY(*w, key & 7) > 0) *w -= 1ull << (7 * (key & 7));
+                    }
                 } else {  // ackPendingProperties (segmentPropertiesManager.ts:15-28)
                     uint64_t pk = pkp[sl];
                     if (rewrite && MT_PK_RW(pk) > 0) pk -= 1ull << 56;
@@ -1577,6 +1648,9 @@ struct Wave {
                 const uint32_t Lo = s.lc.glo;
                 const uint32_t gt = gtp[Lo % GN];
                 const bool rewrite = op.flags & MT_F_REWRITE;
+                // (a wide form's record: its type byte carries MT_OP_WIDE and the pair count's high bits)
+                const uint8_t ty = W ? (uint8_t)MT_OP_BASE(op) : op.type;
+                if constexpr (W) ackw = (op.type & MT_OP_WIDE) != 0;
                 block_starts();
                 const int n = s.n;
                 for (int base = 0; base < n; base += 64) {  // the original members, in document order
@@ -1590,7 +1664,7 @@ struct Wave {
                     while (m) {
                         const int fl = first_lane(m);
                         m &= m - 1;
-                        ack_one(base + fl, S, Lo, op.type, pairs, np, rewrite);
+                        ack_one(base + fl, S, Lo, ty, pairs, np, rewrite);
                         if (s.err) return;
                     }
                 }
@@ -1615,7 +1689,7 @@ struct Wave {
                         if (hm) k = base + first_lane(hm);
                     }
                     if (k < 0) break;
-                    ack_one(k, S, Lo, op.type, pairs, np, rewrite);
+                    ack_one(k, S, Lo, ty, pairs, np, rewrite);
                     if (s.err) return;
                 }
                 sync();
@@ -1635,7 +1709,9 @@ struct Wave {
     MT_DEV void op_regen(const mt_op_rec& op, const uint8_t* payload) {
         if constexpr (LOC) {
             const int32_t S = MT_SEQ_REGEN;
-            if (s.lc.own < 0 || (int)op.client != s.lc.own || op.type > MT_OP_ANNOTATE) return fail(MT_DERR_BAD_OP, S);
+            // (the wide form's record may carry MT_OP_WIDE and the pair count's high bits in its type byte)
+            if (s.lc.own < 0 || (int)op.client != s.lc.own || (W ? MT_OP_TYPE(op) : op.type) > MT_OP_ANNOTATE)
+                return fail(MT_DERR_BAD_OP, S);
             if (s.lc.glo == s.lc.ghi) return fail(MT_DERR_BAD_OP, S);
             const int np = MT_OP_NPAIRS(op);
             const uint8_t* opairs = payload + op.payload_off + (op.payload_len - 2 * np);
@@ -1679,6 +1755,9 @@ struct Wave {
                     ct_publish();
                     sync();
                     const uint32_t len = s.len[sl];
+                    if constexpr (WL) {
+                        if (!regen_one_wide(op, payload, sl, pos)) return;
+                    } else {
                     mt_op_rec r{};
                     r.seq = (int32_t)rix;
                     r.type = op.type;
@@ -1722,6 +1801,10 @@ struct Wave {
                     if (lane == 0)
                         for (int q = 0; q < 2 * nkv; q++) rgp[s.lc.rgpn + (op.type == MT_OP_INSERT ? len : 0) + q] = kv[q];
                     if (!emit_rec(r)) return;
+                    }
+                    if constexpr (WL) {  // (a removal no longer pending leaves no op, and no group)
+                        if (MT_OP_BASE(op) == MT_OP_REMOVE && (lsqp[sl] >> 32) == 0) continue;
+                    }
                     // its own pending group, same localSeq, at the queue's tail
                     if (s.lc.ghi - s.lc.glo >= GN) return fail(MT_DERR_CAPACITY, S);
                     sync();
@@ -1741,6 +1824,89 @@ struct Wave {
             s.lc.glo = Lo + 1;
             sync();
         }
+    }
+
+    // op_regen's one new op in the wide editing form: a wide record (MT_OP_WIDE: UTF-16 units from the
+    // arena, 3-byte pairs, the pair count's bits 4 / 5 in the type byte) when the segment's text, a key
+    // or a value id does not fit the narrow record; an annotate's pairs are the reset op's, as they came.
+    // false: the document halted (the buffer is full).
+    MT_DEV bool regen_one_wide(const mt_op_rec& op, const uint8_t* payload, int sl, int pos) {
+        if constexpr (WL) {
+            const int32_t S = MT_SEQ_REGEN;
+            const uint32_t bt = MT_OP_BASE(op), len = s.len[sl];
+            mt_op_rec r{};
+            r.seq = (int32_t)rix;
+            r.client = (uint16_t)s.lc.own;
+            r.pos1 = pos;
+            r.pos2 = bt == MT_OP_INSERT ? 0 : pos + (int32_t)len;
+            r.payload_off = s.lc.rgpn;
+            uint8_t kv[3 * MT_MAX_KEYS_WIDE];
+            uint32_t nkv = 0, nkb = 0, tbytes = 0;  // pairs, their bytes, the text's bytes
+            bool wide = false;
+            if (bt == MT_OP_INSERT) {  // the segment's spec: its text (or refType) and props
+                const uint8_t f = s.flags[sl];
+                r.flags = (f & MT_SF_MARKER) ? MT_F_MARKER : 0;
+                uint16_t vals[MT_MAX_KEYS_WIDE];
+                uint8_t keys[MT_MAX_KEYS_WIDE];
+                if (f & MT_SF_PDEF) {
+                    r.flags |= MT_F_PROPS;
+                    for (int k = 0; k < (xk_p ? MT_MAX_KEYS_WIDE : 16); k++) {
+                        const uint32_t v = pval(sl, k);
+                        if (!v) continue;
+                        keys[nkv] = (uint8_t)k;
+                        vals[nkv] = (uint16_t)v;
+                        nkv++;
+                        wide = wide || k >= MT_MAX_KEYS || v > MT_MAX_VALUES;
+                    }
+                }
+                bool wt = false;
+                for (uint32_t t = lane; t < len; t += 64) wt = wt || arena[s.toff[sl] + t] > 0xFFu;
+                wide = wide || wave_ballot(wt) != 0;
+                for (uint32_t q = 0; q < nkv; q++) {
+                    kv[nkb++] = keys[q];
+                    kv[nkb++] = (uint8_t)(vals[q] & 0xFFu);
+                    if (wide) kv[nkb++] = (uint8_t)(vals[q] >> 8);
+                }
+                tbytes = wide ? 2u * len : len;
+            } else if (bt == MT_OP_REMOVE) {
+                if ((lsqp[sl] >> 32) == 0) return true;  // no longer locally removed: no op
+            } else {
+                const uint32_t plen = MT_OP_PAIRS_LEN(op);
+                if (op.payload_len < plen) return fail(MT_DERR_BAD_OP, S), false;
+                wide = (op.type & MT_OP_WIDE) != 0;
+                r.flags = op.flags & MT_F_REWRITE;
+                nkv = (uint32_t)MT_OP_NPAIRS(op);
+                if (nkv > (uint32_t)(wide ? MT_MAX_KEYS_WIDE : MT_MAX_KEYS)) return fail(MT_DERR_BAD_OP, S), false;
+                nkb = (wide ? 3u : 2u) * nkv;
+                const uint8_t* opairs = payload + op.payload_off + (op.payload_len - plen);
+                for (uint32_t q = 0; q < nkb; q++) kv[q] = opairs[q];
+            }
+            r.type = (uint8_t)(bt | (wide ? MT_OP_WIDE : 0u) | ((nkv & 16u) ? MT_OP_NP16 : 0u) | ((nkv & 32u) ? MT_OP_NP32 : 0u));
+            r.flags |= (uint8_t)((nkv & 15u) << MT_F_NPAIRS_SHIFT);
+            r.payload_len = tbytes + nkb;
+            if (s.lc.rgn >= MT_RG_RECS || s.lc.rgpn + r.payload_len > MT_RG_BYTES) return fail(MT_DERR_CAPACITY, S), false;
+            if (bt == MT_OP_INSERT) {
+                for (uint32_t t = lane; t < len; t += 64) {
+                    const uint32_t c = arena[s.toff[sl] + t];
+                    if (wide) {
+                        rgp[s.lc.rgpn + 2 * t] = (uint8_t)(c & 0xFFu);
+                        rgp[s.lc.rgpn + 2 * t + 1] = (uint8_t)(c >> 8);
+                    } else {
+                        rgp[s.lc.rgpn + t] = (uint8_t)c;
+                    }
+                }
+            }
+            if (lane == 0) {
+                for (uint32_t q = 0; q < nkb; q++) rgp[s.lc.rgpn + tbytes + q] = kv[q];
+                rg[s.lc.rgn] = r;
+            }
+            sync();
+            s.lc.rgn = s.lc.rgn + 1;
+            s.lc.rgpn = s.lc.rgpn + r.payload_len;
+            sync();
+            return true;
+        }
+        return false;
     }
 
     // Client.updateSeqNumbers + MergeTree.setMinSeq (client.ts:821-828, mergeTree.ts:1718-1736)
@@ -1769,8 +1935,9 @@ struct Wave {
             s.lc.own = C;
             sync();
         }
-        // (the editing client may be short id 0, the reference's own id, client.ts:1057-1062; its
-        // document stays narrow: the editing form has no wide state)
+        if constexpr (W) return apply_local_wide(op, payload);
+        // (the editing client may be short id 0, the reference's own id, client.ts:1057-1062; a record
+        // past the narrow limits reaches only the wide editing form: mt_bin_kernel routes its document)
         if (C != s.lc.own || C >= MT_MAX_CLIENTS || (op.type & MT_OP_WIDE)) return fail(MT_DERR_LIMITS, -1);
         if (op.payload_len < (uint32_t)(2 * np) || !MT_OP_NO_TEXT_OK(op)) return fail(MT_DERR_BAD_OP, -1);
         if (s.lc.ghi - s.lc.glo >= GN) return fail(MT_DERR_CAPACITY, -1);
@@ -1804,15 +1971,62 @@ struct Wave {
         }
         if (ev && s.evn > (int)evcap) fail(MT_DERR_EVENTS, -1);
     }
+    // apply_local in the wide editing form: the record narrow or wide (UTF-16 text, 3-byte pairs, up to
+    // 32 of them), the editing client any wide id.  An insert at a reference's leaf stays refused on a
+    // wide document.
+    MT_DEV void apply_local_wide(const mt_op_rec& op, const uint8_t* payload) {
+        if constexpr (WL) {
+            const int np = MT_OP_NPAIRS(op);
+            const int C = op.client;
+            const int type = MT_OP_TYPE(op);
+            const bool wop = (op.type & MT_OP_WIDE) != 0;
+            const uint32_t plen = MT_OP_PAIRS_LEN(op);
+            if (C != s.lc.own || C >= MT_MAX_CLIENTS_WIDE || C == MT_CLIENT_NONCOLLAB || type == MT_OP_INSERT_AT)
+                return fail(MT_DERR_LIMITS, -1);
+            if (op.payload_len < plen || (wop && ((op.payload_len - plen) & 1u)) || !MT_OP_NO_TEXT_OK(op))
+                return fail(MT_DERR_BAD_OP, -1);
+            if (s.lc.ghi - s.lc.glo >= GN) return fail(MT_DERR_CAPACITY, -1);
+            const uint8_t* pay = payload + op.payload_off;
+            const int tlen = (int)((op.payload_len - plen) >> (wop ? 1 : 0));  // text code units
+            const Pairs pr{pay + (op.payload_len - plen), np, wop};
+            for (int q = 0; q < np; q++)
+                if (pr.key(q) >= pr.key_limit() || (pr.key(q) >= 16 && !xk_p)) return fail(MT_DERR_LIMITS, -1);
+            mt_op_rec o = op;
+            o.ref_seq = s.cur_seq;
+            s.evseq = -1;
+            const int L = scan(o.ref_seq, C);
+            if (type == MT_OP_INSERT && tlen <= 0) return;
+            sync();
+            s.lc.lseq = s.lc.lseq + 1;
+            sync();
+            if (type == MT_OP_INSERT) {
+                if (o.pos1 < 0 || o.pos1 > L) return fail(MT_DERR_INSERT_FAILED, -1);
+                op_insert(o, pay, tlen, pr);
+            } else {
+                if (o.pos1 < 0 || o.pos2 > L || o.pos1 >= o.pos2) return fail(MT_DERR_BAD_OP, -1);  // getValidOpRange
+                op_range(o, pr);
+            }
+            if (ev && s.evn > (int)evcap) fail(MT_DERR_EVENTS, -1);
+        }
+    }
     MT_DEV void apply_ack(const mt_op_rec& op, const uint8_t* payload) {
         const int np = MT_OP_NPAIRS(op);
         const int32_t S = op.seq;
         s.evseq = S;
         if (!(s.cur_seq <= S)) return fail(MT_DERR_SEQ_ORDER, S);                                  // client.ts:824
         if (!(op.msn <= S) || !(s.min_seq <= op.msn)) return fail(MT_DERR_MSN_ORDER, S);           // :826
-        if (op.type & MT_OP_WIDE) return fail(MT_DERR_LIMITS, S);
-        if (op.payload_len < (uint32_t)(2 * np) || !MT_OP_NO_TEXT_OK(op)) return fail(MT_DERR_BAD_OP, S);
-        op_ack(op, payload + op.payload_off + (op.payload_len - 2 * np), np);
+        if constexpr (W) {  // (the ack may be a wide record: 3-byte pairs)
+            const uint32_t plen = MT_OP_PAIRS_LEN(op);
+            if (op.payload_len < plen || !MT_OP_NO_TEXT_OK(op)) return fail(MT_DERR_BAD_OP, S);
+            const Pairs pr{payload + op.payload_off + (op.payload_len - plen), np, (op.type & MT_OP_WIDE) != 0};
+            for (int q = 0; q < np; q++)
+                if (pr.key(q) >= pr.key_limit()) return fail(MT_DERR_LIMITS, S);
+            op_ack(op, payload + op.payload_off + (op.payload_len - plen), np);
+        } else {
+            if (op.type & MT_OP_WIDE) return fail(MT_DERR_LIMITS, S);
+            if (op.payload_len < (uint32_t)(2 * np) || !MT_OP_NO_TEXT_OK(op)) return fail(MT_DERR_BAD_OP, S);
+            op_ack(op, payload + op.payload_off + (op.payload_len - 2 * np), np);
+        }
         if (s.err) return;
         if (!(op.flags & MT_F_GROUP_MORE)) update_seq(op.msn, S);
         if (ev && s.evn > (int)evcap) fail(MT_DERR_EVENTS, S);
@@ -2222,6 +2436,14 @@ struct Wave {
                 ctp[i] = has ? lr.ct[i] : 0u;
                 lsqp[i] = has ? lr.lsq[i] : 0ull;
             }
+            if constexpr (WL) {
+                // (the counts of keys 8..31: stored by this form only -- a document that was narrow, or
+                // an observer, at its last store has none pending)
+                const uint32_t wx = g.locwx[d];
+                const bool hasw = has && was_wide && wx != MT_NO_ROW;
+                const uint64_t* row = g.pkw + (size_t)(hasw ? wx : 0u) * MT_LOC_BIGCAP * MT_PKW_WORDS;
+                for (int i = lane; i < n * MT_PKW_WORDS; i += 64) pkwp[i] = hasw ? row[i] : 0ull;
+            }
             ct_publish();
         }
         sync();
@@ -2346,7 +2568,8 @@ struct Wave {
             if (lane == 0) {
                 const uint32_t keep = s.wide & ~((0xFFu << MT_WIDE_OVN_SHIFT) | MT_WIDE_XOV);
                 g.sc[d].wide = keep | (xk_p ? MT_WIDE_XKV : 0u) | (xo_p && ovn > 16 ? MT_WIDE_XOV : 0u) |
-                               ((uint32_t)ovn << MT_WIDE_OVN_SHIFT);
+                               ((uint32_t)ovn << MT_WIDE_OVN_SHIFT) |
+                               (LOC && GW > 1 && s.lc.own >= 0 ? MT_WIDE_GROUPS : 0u);
             }
         }
         if constexpr (LOC) {
@@ -2363,6 +2586,10 @@ struct Wave {
                     lr.pk[i] = pkp[sl];
                     lr.ct[i] = ctp[sl];
                     lr.lsq[i] = lsqp[sl];
+                    if constexpr (WL) {  // (loc_admit: the document has its row of the wide pool)
+                        uint64_t* row = g.pkw + ((size_t)g.locwx[d] * MT_LOC_BIGCAP + i) * MT_PKW_WORDS;
+                        for (int q = 0; q < MT_PKW_WORDS; q++) row[q] = pkwp[MT_PKW_WORDS * sl + q];
+                    }
                 }
                 if (lane == 0) {
                     g.loc[d].own = s.lc.own;
@@ -2397,13 +2624,14 @@ struct GenArgs {
 
 // An editing document enters the editing form at CAP slots only if this launch's ops cannot outgrow
 // it (the form cannot move a document between capacities mid-launch); otherwise it halts with
-// MT_DERR_CAPACITY, and a wide document with MT_DERR_LIMITS (no local edits in the wide form).
+// MT_DERR_CAPACITY, and a wide document in a narrow editing form with MT_DERR_LIMITS (mt_bin_kernel
+// sends it to the wide editing form, W).
 // MT_DERR_CAPACITY too when the engine could not give the document the pool rows its form needs.
-template <int CAP, int GW = 1>
+template <int CAP, int GW = 1, bool W = false>
 MT_DEV bool loc_admit(const mt_gstate& g, const mt_op_rec* ops, uint32_t d, uint32_t a, uint32_t b) {
     using LS = Lds<CAP, true>;
     const mt_doc_scalars& sc = g.sc[d];
-    if (sc.wide & MT_WIDE_DOC) {
+    if (!W && (sc.wide & MT_WIDE_DOC)) {
         if (threadIdx.x == 0 && !sc.err) {
             g.sc[d].err = MT_DERR_LIMITS;
             g.sc[d].err_seq = ops[a].seq;
@@ -2415,7 +2643,7 @@ MT_DEV bool loc_admit(const mt_gstate& g, const mt_op_rec* ops, uint32_t d, uint
     for (int L = 1; L < sc.nlev; L++) ib_need = max(ib_need, sc.nb[L]);
     if (!(sc.nseg + 2 * nops + (int)sc.n_empty + 1 <= CAP && sc.nb[0] + 2 * nops + 1 <= LS::LB &&
           ib_need + nops + 1 <= LS::IB && sc.heap_n + 4 * nops + 16 <= LS::H && CAP <= loc_row(g, d).cap &&
-          (GW == 1 || g.locgx[d] != MT_NO_ROW))) {
+          (GW == 1 || g.locgx[d] != MT_NO_ROW) && (!W || g.locwx[d] != MT_NO_ROW))) {
         if (threadIdx.x == 0 && !sc.err) {
             g.sc[d].err = MT_DERR_CAPACITY;
             g.sc[d].err_seq = ops[a].seq;
@@ -2574,6 +2802,7 @@ __global__ __launch_bounds__(64) void apply_kernel_g(mt_gstate g, const mt_op_re
         wv.lsqp = st.lsq;
         wv.pkp = st.pk;
         wv.gmp = st.gm;
+        if constexpr (W) wv.pkwp = st.pkw;
         if constexpr (GW > 1) {
             wv.gtp = st.lc.gt;
             wv.glsp = st.lc.gls;
@@ -2586,7 +2815,7 @@ __global__ __launch_bounds__(64) void apply_kernel_g(mt_gstate g, const mt_op_re
     const uint32_t a = min(r1, r0 + op_lo);
     const uint32_t b = op_cnt ? min(r1, a + op_cnt) : r1;
     if (a >= b) return;
-    if (LOC && !loc_admit<CAP, GW>(g, ops, d, a, b)) return;
+    if (LOC && !loc_admit<CAP, GW, W>(g, ops, d, a, b)) return;
     wv.load(kernarg_g(), d);
     if (LOC) {
         wv.rg = g.rg + (size_t)d * MT_RG_RECS;
@@ -2637,6 +2866,44 @@ __global__ __launch_bounds__(64) void apply_kernel_wl(mt_gstate g, const mt_op_r
 
 // ------------------------------------------------------------------------------------------
 // host-side launchers (called from mt_engine.cpp)
+// The wide editing form's six kernels are a translation unit of their own (mt_apply_locw.hip, which
+// includes this file with MT_APPLY_LOCW_TU defined): they compile beside the others, not after them.
+#ifdef MT_APPLY_LOCW_TU
+// wide editing documents (mt_bin_kernel's last six buckets; include/mtgpu.h "limits"): the editing form
+// and the wide form in one, its structure in the HBM workspace (n_docs * mt_lds_bytes_loc_wide bytes),
+// at 1024 / 4096 / 8192 slots, gw = 1 or MT_LOC_GW group-mask words per slot
+extern "C" hipError_t mt_launch_apply_loc_wide(int cap_class, int gw, const mt_gstate* g, const mt_op_rec* ops,
+                                               const uint8_t* payload, const uint32_t* row_ptr,
+                                               const uint32_t* doc_ids, uint32_t n_docs, uint32_t op_lo,
+                                               uint32_t op_cnt, uint8_t* ws, hipStream_t stream) {
+    if (n_docs == 0) return hipSuccess;
+    dim3 grid(n_docs), block(64);
+#define MT_LAUNCH_LOCW(CAPV, GWV)                                                                            \
+    if (cap_class == CAPV && gw == GWV) {                                                                    \
+        hipLaunchKernelGGL((mt::apply_kernel_g<CAPV, true, true, GWV>), grid, block, 0, stream, *g, ops,      \
+                           payload, row_ptr, doc_ids, n_docs, op_lo, op_cnt, ws);                            \
+        return hipGetLastError();                                                                            \
+    }
+    MT_LAUNCH_LOCW(1024, 1)
+    MT_LAUNCH_LOCW(4096, 1)
+    MT_LAUNCH_LOCW(8192, 1)
+    MT_LAUNCH_LOCW(1024, MT_LOC_GW)
+    MT_LAUNCH_LOCW(4096, MT_LOC_GW)
+    MT_LAUNCH_LOCW(8192, MT_LOC_GW)
+#undef MT_LAUNCH_LOCW
+    return hipErrorInvalidValue;
+}
+
+extern "C" size_t mt_lds_bytes_loc_wide(int cap_class, int gw) {
+    if (gw == 1 && cap_class == 1024) return sizeof(mt::Lds<1024, true, true>);
+    if (gw == 1 && cap_class == 4096) return sizeof(mt::Lds<4096, true, true>);
+    if (gw == 1 && cap_class == 8192) return sizeof(mt::Lds<8192, true, true>);
+    if (gw == MT_LOC_GW && cap_class == 1024) return sizeof(mt::Lds<1024, true, true, MT_LOC_GW>);
+    if (gw == MT_LOC_GW && cap_class == 4096) return sizeof(mt::Lds<4096, true, true, MT_LOC_GW>);
+    if (gw == MT_LOC_GW && cap_class == 8192) return sizeof(mt::Lds<8192, true, true, MT_LOC_GW>);
+    return 0;
+}
+#else
 static hipError_t launch_any(int cap_class, bool gen, const mt_gstate* g, mt_op_rec* ops, uint8_t* payload,
                              const uint32_t* row_ptr, const uint32_t* doc_ids, uint32_t n_docs, uint32_t op_lo,
                              uint32_t op_cnt, const mt::GenArgs& ga, hipStream_t stream) {
@@ -2843,3 +3110,4 @@ extern "C" size_t mt_lds_bytes(int cap_class) {
         default: return 0;
     }
 }
+#endif  // MT_APPLY_LOCW_TU

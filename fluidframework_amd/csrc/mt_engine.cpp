@@ -30,8 +30,9 @@ namespace {
 const int32_t kClasses[kNumClasses] = {128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024,
                                        2048, 4096, 8192, 16384, 32768, 65472};
 // the editing forms' capacities and group-mask words per slot (kLocForms, mt_engine_impl.h)
-const int32_t kLocCaps[kLocForms] = {256, 512, 2048, 4096, 1024, 4096, 8192, 8192};
-const int32_t kLocGW[kLocForms] = {1, 1, 1, 1, MT_LOC_GW, MT_LOC_GW, 1, MT_LOC_GW};
+const int32_t kLocCaps[kLocForms] = {256, 512, 2048, 4096, 1024, 4096, 8192, 8192, 1024, 4096, 8192, 1024, 4096, 8192};
+const int32_t kLocGW[kLocForms] = {1, 1, 1, 1, MT_LOC_GW, MT_LOC_GW, 1, MT_LOC_GW, 1, 1, 1, MT_LOC_GW, MT_LOC_GW, MT_LOC_GW};
+constexpr int kFirstLocWide = 8;  // the wide editing forms (mt_launch_apply_loc_wide): the last six
 // {CAP, LB, IB, H} per class: at most mt::Lds<lds_cap(CAP)>'s and mtr::RLds<CAP/64>'s (the 128 and 192
 // classes take the 256 class's block and heap limits, which both hold: with CAP / 2 blocks and
 // CAP / 8 + 8 interior blocks no b = 32 launch fits them)
@@ -126,6 +127,21 @@ static bool grow_gx(mt_engine* e, uint32_t rows) {
     e->gxcap = rows;
     return true;
 }
+// the wide editing documents' pool: per row the pending property counts of keys 8..31 (mt_state.h pkw)
+static bool grow_wx(mt_engine* e, uint32_t rows) {
+    mt_gstate& g = e->g;
+    const size_t R = (size_t)MT_LOC_BIGCAP * MT_PKW_WORDS * sizeof(uint64_t);
+    void* pw = nullptr;
+    if (!pool_alloc(&pw, rows * R)) return false;
+    if (e->nwx && hipMemcpy(pw, g.pkw, e->nwx * R, hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(pw);
+        return false;
+    }
+    if (g.pkw) (void)hipFree(g.pkw);
+    g.pkw = (uint64_t*)pw;
+    e->wxcap = rows;
+    return true;
+}
 // rows for `want` more documents: double the pool (at least 16 rows), else exactly what is needed;
 // returns how many of them got rows
 template <class Grow>
@@ -138,16 +154,17 @@ static uint32_t pool_reserve(uint32_t used, uint32_t cap, uint32_t want, Grow gr
 }
 // Assigns the rows of one tick's editing buckets (bk: the bucket's index in d_ids); the documents that
 // get no row halt in the kernel with MT_DERR_CAPACITY (mt_apply.hip loc_admit)
-static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt, bool big, bool gx) {
+static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt, bool big, bool gx, bool wx = false) {
     mt_gstate& g = e->g;
     e->h_bucket.resize(cnt);
     HIP_OK(hipMemcpy(e->h_bucket.data(), ids, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> nb, ng;
+    std::vector<uint32_t> nb, ng, nw;
     for (uint32_t d : e->h_bucket) {
         if (big && e->h_locbig[d] == MT_NO_ROW) nb.push_back(d);
         if (gx && e->h_locgx[d] == MT_NO_ROW) ng.push_back(d);
+        if (wx && e->h_locwx[d] == MT_NO_ROW) nw.push_back(d);
     }
-    if (nb.empty() && ng.empty()) return MT_OK;
+    if (nb.empty() && ng.empty() && nw.empty()) return MT_OK;
     HIP_OK(hipDeviceSynchronize());
     const uint32_t rb = std::min<uint32_t>((uint32_t)nb.size(), (uint32_t)e->free_big.size());
     const uint32_t kb = rb + pool_reserve(e->nbig, e->bigcap, (uint32_t)nb.size() - rb,
@@ -184,6 +201,23 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
         e->h_locgx[d] = r;
         HIP_OK(hipMemcpy(g.locgx + d, &r, 4, hipMemcpyHostToDevice));
     }
+    // (a wide-pool row starts unread: the form loads zeros for a document that was narrow, or an
+    // observer, at its last store -- mt_apply.hip load)
+    const uint32_t rw = std::min<uint32_t>((uint32_t)nw.size(), (uint32_t)e->free_wx.size());
+    const uint32_t kw = rw + pool_reserve(e->nwx, e->wxcap, (uint32_t)nw.size() - rw,
+                                          [&](uint32_t r) { return grow_wx(e, r); });
+    for (uint32_t i = 0; i < kw; i++) {
+        uint32_t r;
+        if (i < rw) {
+            r = e->free_wx.back();
+            e->free_wx.pop_back();
+        } else {
+            r = e->nwx++;
+        }
+        const uint32_t d = nw[i];
+        e->h_locwx[d] = r;
+        HIP_OK(hipMemcpy(g.locwx + d, &r, 4, hipMemcpyHostToDevice));
+    }
     return MT_OK;
 }
 
@@ -192,12 +226,13 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
 // row).  The host mirrors are updated per document; the device tables get one copy of the changed
 // span each and one synchronization (not two round trips per document).
 static mt_status release_loc_rows(mt_engine* e, const uint32_t* docs, uint32_t n) {
-    uint32_t lo[2] = {UINT32_MAX, UINT32_MAX}, hi[2] = {0, 0};
-    std::vector<uint32_t>* mirror[2] = {&e->h_locbig, &e->h_locgx};
-    std::vector<uint32_t>* freel[2] = {&e->free_big, &e->free_gx};
+    constexpr int P = 3;  // the pools
+    uint32_t lo[P] = {UINT32_MAX, UINT32_MAX, UINT32_MAX}, hi[P] = {0, 0, 0};
+    std::vector<uint32_t>* mirror[P] = {&e->h_locbig, &e->h_locgx, &e->h_locwx};
+    std::vector<uint32_t>* freel[P] = {&e->free_big, &e->free_gx, &e->free_wx};
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t d = docs[i];
-        for (int k = 0; k < 2; k++) {
+        for (int k = 0; k < P; k++) {
             if (d >= mirror[k]->size() || (*mirror[k])[d] == MT_NO_ROW) continue;
             freel[k]->push_back((*mirror[k])[d]);
             (*mirror[k])[d] = MT_NO_ROW;
@@ -205,9 +240,9 @@ static mt_status release_loc_rows(mt_engine* e, const uint32_t* docs, uint32_t n
             hi[k] = std::max(hi[k], d + 1);
         }
     }
-    uint32_t* dev[2] = {e->g.locbig, e->g.locgx};
+    uint32_t* dev[P] = {e->g.locbig, e->g.locgx, e->g.locwx};
     bool any = false;
-    for (int k = 0; k < 2; k++) {
+    for (int k = 0; k < P; k++) {
         if (lo[k] >= hi[k]) continue;
         HIP_OK(hipMemcpyAsync(dev[k] + lo[k], mirror[k]->data() + lo[k], 4ull * (hi[k] - lo[k]), hipMemcpyHostToDevice,
                               e->stream));
@@ -301,7 +336,7 @@ mt_status mt_engine_create(const mt_cfg* cfg, mt_engine** out) {
         (st = dalloc(e, &g.gmxs, D * MT_LOC_CAP)) || (st = dalloc(e, &g.loc, D)) ||
         (st = dalloc(e, &g.lsq, D * MT_LOC_CAP)) || (st = dalloc(e, &g.rg, D * MT_RG_RECS)) ||
         (st = dalloc(e, &g.rgp, D * MT_RG_BYTES)) || (st = dalloc(e, &g.locbig, D)) ||
-        (st = dalloc(e, &g.locgx, D)) ||
+        (st = dalloc(e, &g.locgx, D)) || (st = dalloc(e, &g.locwx, D)) ||
         // (the editing documents' and the wide documents' buckets after the capacity classes)
         (st = dalloc(e, &e->d_counts, kCounts)) || (st = dalloc(e, &e->d_acc, kBuckets)) ||
         (st = dalloc(e, &e->d_ids, D * kBuckets))) {
@@ -317,8 +352,10 @@ mt_status mt_engine_create(const mt_cfg* cfg, mt_engine** out) {
     HIP_OK(hipMemcpy(e->d_classes, kClassParams, sizeof(kClassParams), hipMemcpyHostToDevice));
     HIP_OK(hipMemset(g.locbig, 0xFF, D * sizeof(uint32_t)));  // MT_NO_ROW
     HIP_OK(hipMemset(g.locgx, 0xFF, D * sizeof(uint32_t)));
+    HIP_OK(hipMemset(g.locwx, 0xFF, D * sizeof(uint32_t)));
     e->h_locbig.assign(D, MT_NO_ROW);
     e->h_locgx.assign(D, MT_NO_ROW);
+    e->h_locwx.assign(D, MT_NO_ROW);
     {
         const char* v = getenv("MTGPU_ENGINE");
         // the register engine keeps text offsets in 16 bits (textcap <= 64 KiB)
@@ -355,7 +392,7 @@ mt_status mt_engine_destroy(mt_engine* e) {
     refs_free(e);
     if (e->ws) (void)hipFree(e->ws);
     for (void* p : {(void*)e->g.gmb, (void*)e->g.pkb, (void*)e->g.ctb, (void*)e->g.lsqb, (void*)e->g.gmx,
-                    (void*)e->g.locx})
+                    (void*)e->g.locx, (void*)e->g.pkw})
         if (p) (void)hipFree(p);
     if (e->h_counts) hipHostFree(e->h_counts);
     for (auto ev : e->kev) (void)hipEventDestroy(ev);
@@ -400,15 +437,18 @@ mt_status mt_docs_init(mt_engine* e, uint32_t n_docs) {
     e->gen++;
     e->lkeys.assign(e->cfg.max_docs, (uint16_t)MT_NO_LABEL_KEYS);
     // every document starts over: the editing pools' rows are all free again
-    if (e->nbig || e->ngx) {
+    if (e->nbig || e->ngx || e->nwx) {
         HIP_OK(hipStreamSynchronize(e->stream));
         HIP_OK(hipMemset(e->g.locbig, 0xFF, e->cfg.max_docs * sizeof(uint32_t)));  // MT_NO_ROW
         HIP_OK(hipMemset(e->g.locgx, 0xFF, e->cfg.max_docs * sizeof(uint32_t)));
+        HIP_OK(hipMemset(e->g.locwx, 0xFF, e->cfg.max_docs * sizeof(uint32_t)));
         e->h_locbig.assign(e->cfg.max_docs, MT_NO_ROW);
         e->h_locgx.assign(e->cfg.max_docs, MT_NO_ROW);
-        e->nbig = e->ngx = 0;
+        e->h_locwx.assign(e->cfg.max_docs, MT_NO_ROW);
+        e->nbig = e->ngx = e->nwx = 0;
         e->free_big.clear();
         e->free_gx.clear();
+        e->free_wx.clear();
     }
     HIP_OK(mt_launch_init(&e->g, n_docs, e->stream));
     HIP_OK(refs_clear(e));  // (rows still in the event buffer: the next fold only moves the cursors past them)
@@ -600,12 +640,13 @@ static mt_status apply_launches(mt_engine* e, const mt_batch* b, uint32_t& nk) {
         size_t lws_off[kLocForms] = {};
         for (int q = 0; q < kLocForms; q++) {
             const uint32_t cnt = e->h_counts[lds_base + 2 * e->first_lds + q];
-            if ((kLocCaps[q] <= MT_LOC_CAP && kLocGW[q] == 1) || !cnt) continue;
+            const bool wx = q >= kFirstLocWide;
+            if ((kLocCaps[q] <= MT_LOC_CAP && kLocGW[q] == 1 && !wx) || !cnt) continue;
             const mt_status ls = assign_loc_rows(e, e->d_ids + (size_t)(lds_base + 2 * e->first_lds + q) * b->n_docs,
-                                                 cnt, kLocCaps[q] > MT_LOC_CAP, kLocGW[q] > 1);
+                                                 cnt, kLocCaps[q] > MT_LOC_CAP, kLocGW[q] > 1, wx);
             if (ls) return ls;
             lws_off[q] = need;
-            need += (size_t)cnt * mt_lds_bytes_loc(kLocCaps[q], kLocGW[q]);
+            need += (size_t)cnt * (wx ? mt_lds_bytes_loc_wide(kLocCaps[q], kLocGW[q]) : mt_lds_bytes_loc(kLocCaps[q], kLocGW[q]));
         }
         if (need > e->ws_bytes) {
             HIP_OK(hipDeviceSynchronize());
@@ -725,7 +766,11 @@ static mt_status apply_launches(mt_engine* e, const mt_batch* b, uint32_t& nk) {
                 e->kev.push_back(ev);
             }
             HIP_OK(hipEventRecord(e->kev[2 * nk], e->stream));
-            if (q >= 0 && (kLocCaps[q] > MT_LOC_CAP || kLocGW[q] > 1))
+            if (q >= kFirstLocWide)
+                HIP_OK(mt_launch_apply_loc_wide(kLocCaps[q], kLocGW[q], &e->g, b->ops, b->payload, b->row_ptr,
+                                                e->d_ids + (size_t)bk * b->n_docs, cnt, lo, per, e->ws + lws_off[q],
+                                                e->stream));
+            else if (q >= 0 && (kLocCaps[q] > MT_LOC_CAP || kLocGW[q] > 1))
                 HIP_OK(mt_launch_apply_loc_big(kLocCaps[q], kLocGW[q], &e->g, b->ops, b->payload, b->row_ptr,
                                                e->d_ids + (size_t)bk * b->n_docs, cnt, lo, per, e->ws + lws_off[q],
                                                e->stream));
@@ -1357,6 +1402,7 @@ mt_status mt_last_apply_class_stats(mt_engine* e, uint32_t cls, uint32_t* capaci
                     : q < (uint32_t)kFirstLds           ? (MT_CLASS_LDS | (uint32_t)kClasses[q])
                     : q < (uint32_t)(2 * kFirstLds)     ? (MT_CLASS_C64 | (uint32_t)kClasses[q - kFirstLds])
                                                         : (MT_CLASS_EDITING | (kLocGW[q - 2 * kFirstLds] > 1 ? MT_CLASS_GROUPS : 0u) |
+                                                           (q - 2 * kFirstLds >= (uint32_t)kFirstLocWide ? MT_CLASS_WIDE : 0u) |
                                                            (uint32_t)kLocCaps[q - 2 * kFirstLds]);
     }
     if (kernel_ms) *kernel_ms = e->cls_ms[cls];
@@ -1368,7 +1414,11 @@ mt_status mt_last_apply_class_stats(mt_engine* e, uint32_t cls, uint32_t* capaci
 mt_status mt_class_kernel_name(mt_engine* e, uint32_t capacity, char* buf, uint64_t cap) {
     if (!e || !buf || !cap) return MT_ERR_ARG;
     char tmp[96];
-    if ((capacity & MT_CLASS_EDITING) && (capacity & MT_CLASS_GROUPS))
+    if ((capacity & MT_CLASS_EDITING) && (capacity & MT_CLASS_WIDE))
+        snprintf(tmp, sizeof tmp, "mt::apply_kernel_g<%u, true, true, %d>",
+                 capacity & ~(uint32_t)(MT_CLASS_EDITING | MT_CLASS_WIDE | MT_CLASS_GROUPS),
+                 (capacity & MT_CLASS_GROUPS) ? MT_LOC_GW : 1);
+    else if ((capacity & MT_CLASS_EDITING) && (capacity & MT_CLASS_GROUPS))
         snprintf(tmp, sizeof tmp, "mt::apply_kernel_g<%u, false, true, %d>",
                  capacity & ~(uint32_t)(MT_CLASS_EDITING | MT_CLASS_GROUPS), MT_LOC_GW);
     else if ((capacity & MT_CLASS_EDITING) && (capacity & ~(uint32_t)MT_CLASS_EDITING) > MT_LOC_CAP)

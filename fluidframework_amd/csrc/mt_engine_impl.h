@@ -32,8 +32,9 @@ constexpr int kWideClasses = kNumClasses - kFirstWide;
 // (then the editing documents that fit 256 / 512 slots: the editing form at that size; then those
 // above MT_LOC_CAP = 1024: its HBM-workspace form at 2048 / 4096; then those past 64 pending edits
 // (MT_WIDE_GROUPS): the HBM-workspace form with 4 group-mask words per slot at 1024 / 4096; then
-// both forms at 8192)
-constexpr int kLocForms = 8;
+// both forms at 8192; then the wide editing forms (include/mtgpu.h "limits": an editing document past the
+// narrow limits) at 1024 / 4096 / 8192 slots, with one group-mask word per slot and then with MT_LOC_GW)
+constexpr int kLocForms = 14;
 constexpr int kBuckets = kNumClasses + 1 + kWideClasses + 2 * kFirstLds + kLocForms;
 // binning's counters: one per bucket, then per wide bucket the documents that stage the wide form's
 // extension (mt_state.h MT_WIDE_XK / MT_WIDE_XO) -- their launch takes an HBM region for it
@@ -92,9 +93,9 @@ struct mt_engine {
     uint64_t gen = 0;  // bumped by every call that can change document state (snap_cache's key)
     std::vector<uint16_t> lkeys;  // per document: its declared label keys (mt_set_label_keys), host copy
     // the editing documents' pool rows (mt_state.h locbig / locgx): host copies, rows in use, rows held
-    std::vector<uint32_t> h_locbig, h_locgx, h_bucket;
-    uint32_t nbig = 0, bigcap = 0, ngx = 0, gxcap = 0;
-    std::vector<uint32_t> free_big, free_gx;  // rows given back by reloaded documents, reused first
+    std::vector<uint32_t> h_locbig, h_locgx, h_locwx, h_bucket;
+    uint32_t nbig = 0, bigcap = 0, ngx = 0, gxcap = 0, nwx = 0, wxcap = 0;
+    std::vector<uint32_t> free_big, free_gx, free_wx;  // rows given back by reloaded documents, reused first
     // mt_submit_ticks: a ring of device slots; tick k is copied into slot k % kRing on the h2d
     // stream while the ticks before it apply, and the slot is reused once its tick has applied (and
     // its tickets have gone back on the d2h stream)

@@ -30,6 +30,10 @@ hipError_t mt_launch_apply_wide(int cap_class, const mt_gstate* g, const mt_op_r
 hipError_t mt_launch_apply_loc_big(int cap_class, int gw, const mt_gstate* g, const mt_op_rec* ops,
                                    const uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
                                    uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, uint8_t* ws, hipStream_t stream);
+// (the wide editing form: cap_class 1024 / 4096 / 8192, gw 1 or MT_LOC_GW; ws: n_docs * mt_lds_bytes_loc_wide)
+hipError_t mt_launch_apply_loc_wide(int cap_class, int gw, const mt_gstate* g, const mt_op_rec* ops,
+                                    const uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
+                                    uint32_t n_docs, uint32_t op_lo, uint32_t op_cnt, uint8_t* ws, hipStream_t stream);
 hipError_t mt_launch_gen(int cap_class, const mt_gstate* g, const mt_synth_cfg* cfg, uint32_t doc_id_base,
                          const uint32_t* gids, int32_t* cref, int32_t* stall, uint32_t* pay_used, uint32_t paycap,
                          mt_op_rec* ops, uint8_t* payload, const uint32_t* row_ptr, const uint32_t* doc_ids,
@@ -37,6 +41,7 @@ hipError_t mt_launch_gen(int cap_class, const mt_gstate* g, const mt_synth_cfg* 
 size_t mt_lds_bytes(int cap_class);
 size_t mt_lds_bytes_wide(int cap_class);
 size_t mt_lds_bytes_loc(int cap_class, int gw);
+size_t mt_lds_bytes_loc_wide(int cap_class, int gw);
 
 // ---- mt_apply_reg.hip: the register engine
 hipError_t mt_launch_apply_reg(int cap_class, int form, const mt_gstate* g, const mt_op_rec* ops,

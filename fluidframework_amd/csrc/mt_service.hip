@@ -217,7 +217,9 @@ __global__ __launch_bounds__(64) void mt_load_kernel(mt_gstate g, uint32_t n, co
 // the LDS engine at that class's capacity, not at first_lds's; then one per such class for the
 // documents that only need 64-bit overlap sets (a client id above 32): the register engine's C64 form;
 // then the editing documents' 256 / 512-slot forms, their 2048 / 4096-slot HBM-workspace forms and
-// the wide-group forms (MT_WIDE_GROUPS: 256 pending edits) at 1024 / 4096 slots, then both at 8192.
+// the wide-group forms (MT_WIDE_GROUPS: 256 pending edits) at 1024 / 4096 slots, then both at 8192;
+// then the wide editing forms (an editing document that is wide, or turns wide in this launch) at 1024 /
+// 4096 / 8192 slots, and the same three with the wide-group masks.
 // Binning is wave-aggregated: one atomic per (wave, bucket).
 __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr, uint32_t n_docs, uint32_t op_lo,
                               uint32_t op_cnt, const int32_t* __restrict__ classes, int n_classes, int first_lds,
@@ -225,7 +227,7 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                               const mt_op_rec* __restrict__ ops, const uint8_t* __restrict__ payload,
                               unsigned long long* __restrict__ acc) {
     const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n_buckets = n_classes + 1 + (n_classes > first_wide ? n_classes - first_wide : 0) + 2 * first_lds + 8;
+    const int n_buckets = n_classes + 1 + (n_classes > first_wide ? n_classes - first_wide : 0) + 2 * first_lds + 14;
     int c = -1;
     unsigned long long bytes = 0;
     if (d < n_docs) {
@@ -333,6 +335,24 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 }
             }
             const int cls = c;  // the capacity class (before the bucket remaps below)
+            bool halted = false;  // (a wide document on an engine without the wide state)
+            bool wxk = false, wxo = false;  // the extension's parts this launch stages (a wide document)
+            if (wdoc && editing) {
+                // the wide editing form (its bucket: below).  Both flags may be this launch's: the document
+                // enters the form narrow, or as an observer.  The extension is the workspace's own tail.
+                if (!g.ovx) {
+                    g.sc[d].err = MT_DERR_LIMITS;
+                    g.sc[d].err_seq = ops ? ops[a].seq : 0;
+                    c = -1;
+                    halted = true;
+                } else {
+                    wxk = (sc.wide & MT_WIDE_XK) || key16;
+                    wxo = MT_WIDE_OVN(sc.wide) + nrem_hi > 16u;
+                    const uint32_t w0 = g.sc[d].wide;
+                    const uint32_t w1 = (w0 & ~MT_WIDE_XO) | (wxk ? MT_WIDE_XK : 0u) | (wxo ? MT_WIDE_XO : 0u);
+                    if (w1 != w0) g.sc[d].wide = w1;
+                }
+            }
             if (wdoc && !editing) {
                 // the wide form, from the 2048 class up (the wide state is the engine's to allocate:
                 // without it the document halts)
@@ -373,7 +393,7 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 const int lds_base = n_classes + 1 + (n_classes > first_wide ? n_classes - first_wide : 0);
                 c = ((needs_lds || off_win) ? lds_base : lds_base + first_lds) + c;
             }
-            if (editing) {
+            if (editing && !halted) {
                 // the editing documents' buckets (mt_launch_apply_loc): the 1024-slot form at n_classes,
                 // the 256 / 512-slot forms after the C64 buckets (when the chosen class fits them), then
                 // the HBM-workspace forms at 2048 / 4096 / 8192 slots (mt_launch_apply_loc_big)
@@ -387,8 +407,10 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                                   : ebase + 6;
                 // past 64 pending edits (or close: each local edit and each reconnect's op adds a
                 // group): the form with 256 group slots, at 1024 / 4096 / 8192 slots, for good
-                if ((sc.wide & MT_WIDE_GROUPS) || pend + nloc + 4u * nregen > 48u)
-                    c = cap <= 1024 ? ebase + 4 : cap <= 4096 ? ebase + 5 : ebase + 7;
+                const bool groups = (sc.wide & MT_WIDE_GROUPS) || pend + nloc + 4u * nregen > 48u;
+                if (groups) c = cap <= 1024 ? ebase + 4 : cap <= 4096 ? ebase + 5 : ebase + 7;
+                // a wide editing document: the wide editing forms (mt_launch_apply_loc_wide)
+                if (wdoc) c = ebase + 8 + (cap <= 1024 ? 0 : cap <= 4096 ? 1 : 2) + (groups ? 3 : 0);
             }
             if (acc) {
                 // algorithmic bytes of this document's share of the launch (DESIGN.md "Roofline
@@ -400,6 +422,10 @@ __global__ void mt_bin_kernel(mt_gstate g, const uint32_t* __restrict__ row_ptr,
                 // writes by slot during the launch: counted as state in + out like the rest
                 if (editing)
                     st += (unsigned long long)(20u + 8u * ((sc.wide & MT_WIDE_GROUPS) ? MT_LOC_GW : 1u)) * sc.nseg;
+                // a wide editing document's wide state (ovx words 0..3, chi, ph, pxl, pxh; the extension's
+                // parts it stages) and its three further pending-count words
+                if (editing && wdoc)
+                    st += (unsigned long long)(58u + (wxk ? 32u : 0u) + (wxo ? 32u : 0u) + 8u * MT_PKW_WORDS) * sc.nseg;
                 for (int L = 1; L < sc.nlev; L++) st += (unsigned long long)sc.nb[L];
                 if (!ops) ob = 32ull * (b - a);  // (with records: summed in the pass above)
                 bytes = 2ull * st + ob;

@@ -105,6 +105,10 @@ struct mt_locx {
 // 7 bits per key id 0..7 at bit 7k, the pending rewrite count in bits 56..63
 #define MT_PK_KEY(pk, k) ((uint32_t)((pk) >> (7 * (k))) & 0x7Fu)
 #define MT_PK_RW(pk) ((uint32_t)((pk) >> 56))
+// A wide editing document (MT_WIDE_DOC with an editing client: keys 0..31) keeps three more words per
+// segment, for keys 8..15, 16..23 and 24..31: the same 7-bit saturating fields, key k's at bit 7 (k % 8)
+// of word k / 8 - 1 (mt_gstate.pkw); the rewrite count stays in the first word
+#define MT_PKW_WORDS 3
 
 // One entry of a document's local-reference table: a LocalReference (localReference.ts:20-119) as the
 // segment it sits on -- its ordinal among the linked leaves, -1: detached -- and its offset there.
@@ -216,4 +220,9 @@ struct mt_gstate {
     mt_interval* ivs;  // [doc][ivcap]
     uint32_t* ivn;     // [doc] live intervals
     uint32_t segcap, lbcap, ibcap, hcap, textcap, evcap, refcap, ivcap;
+    // wide editing documents: a row of the wide pool (locwx[doc], or MT_NO_ROW) with the pending property
+    // counts of keys 8..31 ([row][MT_LOC_BIGCAP][MT_PKW_WORDS]), taken when the document first runs in
+    // the wide editing form.  (Last: the kernel argument's earlier fields stay where they were.)
+    uint64_t* pkw;
+    uint32_t* locwx;   // [doc]
 };

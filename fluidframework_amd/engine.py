@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .oplog import OP_DTYPE, OpBatch
+from .oplog import OP_DTYPE, OpBatch, decode_record
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MTGPU_LIB') or os.path.join(HERE, 'libmtgpu.so')
@@ -359,19 +359,15 @@ class MergeEngine:
             if t == 3:  # header: the resetting record's index
                 out.append([int(r['seq']), []])
                 continue
-            fl = int(r['flags'])
-            npairs = (fl >> 3) & 15
-            off, ln = int(r['payload_off']), int(r['payload_len'])
-            body = bytes(pay[off:off + ln])
-            pairs = body[ln - 2 * npairs:]
+            # (narrow or wide: MT_OP_WIDE records carry UTF-16 text, 3-byte pairs and up to 32 of them)
+            t, fl, text, props = decode_record(r, pay)
             if t == 0:
-                props = {str(pairs[2 * q]): int(pairs[2 * q + 1]) for q in range(npairs)} if fl & 2 else None
-                out[-1][1].append([0, int(r['pos1']), 0, body[:ln - 2 * npairs].decode('latin-1'), props, fl & 128])
+                props = None if props is None else {str(k): v for k, v in props.items()}
+                out[-1][1].append([0, int(r['pos1']), 0, text, props, fl & 128])
             elif t == 1:
                 out[-1][1].append([1, int(r['pos1']), int(r['pos2']), None, None, 0])
             else:
-                props = {str(pairs[2 * q]): (int(pairs[2 * q + 1]) or None) for q in range(npairs)}
-                out[-1][1].append([2, int(r['pos1']), int(r['pos2']), None, props, fl & 1])
+                out[-1][1].append([2, int(r['pos1']), int(r['pos2']), None, {str(k): v for k, v in props.items()}, fl & 1])
         return out
 
     def range_stacks(self, queries, cap=64):

@@ -232,6 +232,22 @@ def encode_record(typ, flags=0, text=None, props=None, rel1=None, rel2=None, for
     return t, flags | fbits, data
 
 
+def decode_record(rec, payload):
+    """(base type, flags without the pair count, text | None, props | None) of a record, encode_record's
+    inverse: the text a str (UTF-16 units, lone surrogates kept; None for a remove or an annotate), the
+    props {key id: value id | None} (an insert's only with F_PROPS).  A narrow record has 2-byte pairs and
+    Latin-1 text, a wide one (MT_OP_WIDE) 3-byte pairs, UTF-16 text and up to 32 pairs."""
+    typ, fl = int(rec['type']), int(rec['flags'])
+    wide, base = bool(typ & OP_WIDE), base_type(typ)
+    text_b, pairs_b, _, _ = split_payload(rec, payload)
+    pb = 3 if wide else 2
+    props = {pairs_b[pb * q]: (int.from_bytes(pairs_b[pb * q + 1:pb * q + pb], 'little') or None)
+             for q in range(len(pairs_b) // pb)}
+    if base == INSERT:
+        return base, fl & ~(15 << NPAIRS_SHIFT), decode_text(text_b, wide), props if fl & F_PROPS else None
+    return base, fl & ~(15 << NPAIRS_SHIFT), None, props if base == ANNOTATE else None
+
+
 def build_batch(docs):
     """OpBatch of documents given as lists of (seq, ref, msn, client, type, pos1, pos2, text, props,
     flags[, rel1, rel2]) tuples (encode_record's arguments)."""

@@ -140,7 +140,15 @@ enum mt_op_flags {
  * engine's editing form (in LDS up to MT_LOC_CAP = 1024 segments, then with its structure in an HBM
  * workspace at 2048 / 4096 / 8192; past 64 pending edits at once the workspace form with 256
  * pending-edit slots, for good; at most 8192 segments and 512 pending edits; beyond:
- * MT_DERR_CAPACITY); its delta events include the local edits' callbacks (seq -1). */
+ * MT_DERR_CAPACITY); its delta events include the local edits' callbacks (seq -1).
+ * An editing client's document may be WIDE ("limits" below), by its own edits or by others': local
+ * records, acks and MT_SEQ_REGEN records may carry MT_OP_WIDE (UTF-16 text, 3-byte pairs, keys 0..31,
+ * u16 value ids), the editing client's id may be any wide id, and a narrow editing document turns
+ * wide with edits pending.  It then runs on the wide editing form (the HBM workspace at 1024 / 4096 /
+ * 8192 slots; class statistics MT_CLASS_EDITING | MT_CLASS_WIDE [| MT_CLASS_GROUPS] | capacity), under
+ * the same 8192-segment and 512-pending-edit limits; mt_regen_drain returns wide records where the
+ * text, a key or a value id needs one.  One edit stays refused on a wide document, with
+ * MT_DERR_LIMITS: MT_OP_INSERT_AT (insertAtReferencePositionLocal). */
 #define MT_SEQ_LOCAL (-1)
 /* Reconnect (Client.regeneratePendingOp, client.ts:708-766, 855-893): a record with seq =
  * MT_SEQ_REGEN from the editing client holds the pending op to regenerate (the oldest one): its
@@ -180,7 +188,8 @@ typedef struct mt_op_rec {
  * NonCollabClient, so a host interning more than 253 clients skips it), keys < 32 with u16 value
  * ids, UTF-16 text (2 bytes per code unit in the same arena: half the units), and overlap sets of
  * the ids < 64 plus up to MT_OVX_IDS ids >= 64 per segment.  Wide
- * documents run on the LDS engine's wide form (its structure in an HBM workspace); their extra
+ * documents run on the LDS engine's wide form (its structure in an HBM workspace) -- an editing
+ * client's on the wide editing form, under the same limits (MT_SEQ_LOCAL above); their extra
  * per-segment state (122 B) is allocated by the engine on first need.  Value ids are opaque
  * (equality only) and may be interned per key. */
 #define MT_MAX_CLIENTS 64      /* narrow: short client ids 0..63 (overlap set is a u64 bitmask)  */

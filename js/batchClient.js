@@ -410,9 +410,6 @@ class BatchClient {
         const msg = { sequenceNumber: -1, referenceSequenceNumber: this.currentSeq, minimumSequenceNumber: 0 };
         const r = this._record(msg, op, this._shortId(this.longClientId), false);
         if (r.type === NOOP) return undefined;  // insertSegmentLocal: nothing for an empty segment
-        if ((r.type & OP_WIDE) || r.client >= NARROW_CLIENTS) {
-            throw new Error("BatchClient: an editing client's document stays within the narrow limits (include/mtgpu.h)");
-        }
         this.queue.push(r);
         if (this.engine.recording) this.expect.push({ op });  // a local edit's callback: no sequencedMessage
         this.engine.pending += 1;
@@ -448,18 +445,23 @@ class BatchClient {
         const [recs, pay] = native.regenDrain(this.engine.handle, this.doc);
         const ops = [];
         for (let o = 0; o + REC <= recs.length && recs.length >= REC; o += REC) {
-            const type = recs.readUInt8(o + 14), flags = recs.readUInt8(o + 15);
+            let type = recs.readUInt8(o + 14);
+            const flags = recs.readUInt8(o + 15);
             if (type === NOOP) continue;  // one header per regenerated op
             const pos1 = recs.readInt32LE(o + 16), pos2 = recs.readInt32LE(o + 20);
             const off = recs.readUInt32LE(o + 24), len = recs.readUInt32LE(o + 28);
-            const np = (flags >> 3) & 15;
+            // (a wide record, MT_OP_WIDE: UTF-16 text, 3-byte pairs, the count's bits 4 / 5 in the type)
+            const wide = (type & OP_WIDE) !== 0, pb = wide ? 3 : 2;
+            const np = ((flags >> 3) & 15) | (type & OP_NP16 ? 16 : 0) | (type & OP_NP32 ? 32 : 0);
+            type &= 0x07;
             const props = {};
             for (let q = 0; q < np; q++) {
-                const k = pay.readUInt8(off + len - 2 * np + 2 * q), v = pay.readUInt8(off + len - 2 * np + 2 * q + 1);
+                const at = off + len - pb * np + pb * q;
+                const k = pay.readUInt8(at), v = wide ? pay.readUInt16LE(at + 1) : pay.readUInt8(at + 1);
                 props[this.keys[k]] = v ? this.values[k][v] : null;
             }
             if (type === INSERT) {
-                const text = pay.toString("latin1", off, off + len - 2 * np);
+                const text = pay.toString(wide ? "utf16le" : "latin1", off, off + len - pb * np);
                 let seg;
                 if (flags & F_MARKER) seg = { marker: { refType: text.charCodeAt(0) } };
                 else seg = (flags & F_PROPS) ? { text } : text;
@@ -891,8 +893,8 @@ class BatchClient {
         const msg = { sequenceNumber: -1, referenceSequenceNumber: this.currentSeq, minimumSequenceNumber: 0 };
         const r = this._record(msg, op, this._shortId(this.longClientId), false);
         if (r.type === NOOP) return undefined;
-        if ((r.type & OP_WIDE) || r.client >= NARROW_CLIENTS) {
-            throw new Error("BatchClient: an editing client's document stays within the narrow limits (include/mtgpu.h)");
+        if ((r.type & OP_WIDE) || r.client >= NARROW_CLIENTS) {  // (the device refuses it on a wide document)
+            throw new Error("BatchClient: insertAtReferencePositionLocal stays within the narrow limits (include/mtgpu.h)");
         }
         this.engine._enableRefs();
         this.engine.flush();

@@ -25,7 +25,10 @@ function tuple(op) {
 }
 
 const log = loadLog(process.argv[2]);
-const withEvents = process.argv[3] === "events";
+// "full": the callbacks as with "events", and also the ops the local edits returned (`ops`, as record
+// tuples) and the final getText() (`text`)
+const withFull = process.argv[3] === "full";
+const withEvents = process.argv[3] === "events" || withFull;
 // "seqdelta": SequenceDeltaEvents (js/sequenceDeltaEvent.js) from a "sequenceDelta" listener, one record
 // per event in replay_ref.js's seqdelta form
 const withSeqDelta = process.argv[3] === "seqdelta";
@@ -50,6 +53,7 @@ for (let d = 0; d < log.nDocs; d++) {
     const c = eng.createClient();
     c.startOrUpdateCollaboration(own ? "c" + own.client : "observer");
     const regen = [];
+    c.ops = [];
     c.events = [];
     if (withEvents) {  // the canonical event form of fluidframework_amd/events.py; a local edit's seq is -1
         const seg = (x, pd) => [x.segment.ordinal, x.segment.position === undefined ? -1 : x.segment.position,
@@ -99,6 +103,7 @@ for (let d = 0; d < log.nDocs; d++) {
             r = c.annotateRangeLocal(op.pos1, op.pos2, op.props, op.combiningOp);
         }
         if (!r) throw new Error("local edit rejected");
+        c.ops.push(tuple(r));
     }
     c.regen = regen;
     clients.push(c);
@@ -153,6 +158,10 @@ const out = clients.map((c, d) => {
     try { state = c.getState(); } catch (e) { err = String(e.message || e); }
     const line = c.regen.length ? { doc: d, err, state, regen: c.regen } : { doc: d, err, state };
     if (withEvents || withSeqDelta) line.events = c.events;
+    if (withFull) {
+        line.ops = c.ops;
+        try { line.text = c.getText(); } catch (e) { line.err = String(e.message || e); }
+    }
     if (withReads) return JSON.stringify({ doc: d, err, reads: c.events });
     return JSON.stringify(line);
 });
