@@ -579,10 +579,16 @@ extern "C" hipError_t mt_launch_fixup(const mt_gstate* g, const mt_op_rec* ops, 
     hipLaunchKernelGGL(mt_fixup_kernel, dim3((n_docs + 255) / 256), dim3(256), 0, st, *g, ops, n_docs);
     return hipGetLastError();
 }
-// The leaf block holding segment ib, as its position range [*lo, *hi) ([n, n) for ib < 0)
+// The leaf block on the search path to segment ib, as its position range [*lo, *hi).  ib < 0 (a position
+// past the end): the path is the root alone, which shifts over all its children -- its leaves when it is
+// the only block, [0, n) (they answer with their current labels, tileShift / rangeShift on a leaf), else
+// blocks only, [n, n)
 MT_DEV void mt_leaf_block_of(const mt_gstate& g, uint32_t d, const mt_doc_scalars& sc, int ib, int* lo, int* hi) {
     *lo = *hi = sc.nseg;
-    if (ib < 0) return;
+    if (ib < 0) {
+        if (sc.nlev <= 1) *lo = 0;
+        return;
+    }
     const uint8_t* cnt = g.lbcnt + (size_t)d * g.lbcap;
     const int nb = sc.nb[0];
     int carry = 0;

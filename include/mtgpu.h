@@ -397,7 +397,7 @@ mt_status mt_seg_counts(mt_engine* eng, uint32_t* out, uint32_t n_docs);
 typedef struct mt_tile_query {  /* 48 bytes */
     uint32_t doc;
     int32_t pos;                /* startPos */
-    uint8_t key;                /* key id of "referenceTileLabels" in this document (>= 16: no tiles) */
+    uint8_t key;                /* the document's key id of "referenceTileLabels" (>= MT_MAX_KEYS_WIDE: no tiles) */
     uint8_t preceding;
     uint8_t pad[2];
     uint32_t vmask[8];          /* bit v: value id v's label array holds the label */
