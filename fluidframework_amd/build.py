@@ -6,10 +6,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libmtgpu.so')
-SOURCES = ['mt_apply.hip', 'mt_apply_locw.hip', 'mt_apply_reg.hip', 'mt_service.hip', 'mt_refs.hip', 'mt_intervals.hip', 'mt_text.hip', 'mt_markers.hip', 'mt_deli.hip', 'mt_engine.cpp',
+SOURCES = ['mt_apply.hip', 'mt_apply_locw.hip', 'mt_apply_reg.hip', 'mt_service.hip', 'mt_refs.hip', 'mt_intervals.hip', 'mt_text.hip', 'mt_markers.hip', 'mt_ckpt.hip', 'mt_deli.hip', 'mt_engine.cpp',
            'mt_queries.cpp', 'mt_readout.cpp', 'mt_comm.cpp']
 HEADERS = ['mt_state.h', 'mt_wave.h', 'mt_checksum.h', 'mt_synth.h', 'mt_seqwin.h', 'mt_view.h', 'mt_marker.h', 'mt_launch.h',
-           'mt_engine_impl.h', 'mt_scratch.h', 'mt_reg_lds.h', '../../include/mtgpu.h']
+           'mt_engine_impl.h', 'mt_scratch.h', 'mt_reg_lds.h', 'mt_ckpt.h', '../../include/mtgpu.h']
 # a source that includes another one (the wide editing form's kernels are mt_apply.hip's templates)
 DEPS = {'mt_apply_locw.hip': ['mt_apply.hip']}
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

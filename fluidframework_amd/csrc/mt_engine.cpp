@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "mt_checksum.h"
+#include "mt_ckpt.h"
 #include "mt_engine_impl.h"
 #include "mt_scratch.h"
 
@@ -69,6 +70,16 @@ static mt_status ensure_wide(mt_engine* e) {
         g.ovx = nullptr;  // (the kernels test ovx; the others are freed with the engine)
         return st;
     }
+    return MT_OK;
+}
+// The stale markers' cached label ids (mt_state.h slab / slabx), allocated with the first declared label key
+static mt_status ensure_slab(mt_engine* e) {
+    if (e->g.slab) return MT_OK;
+    uint32_t *p = nullptr, *px = nullptr;
+    if (dalloc(e, &p, (size_t)e->cfg.max_docs * e->g.segcap) || dalloc(e, &px, (size_t)e->cfg.max_docs * e->g.segcap))
+        return MT_ERR_NOMEM;
+    e->g.slab = p;
+    e->g.slabx = px;
     return MT_OK;
 }
 // The editing documents' pools (mt_state.h): a document whose editing form needs more than
@@ -152,6 +163,13 @@ static uint32_t pool_reserve(uint32_t used, uint32_t cap, uint32_t want, Grow gr
     if (grow(need)) return want;
     return cap > used ? cap - used : 0;
 }
+// a pool row for one more document: one given back (the free list) first, else the next unused one
+static uint32_t take_row(std::vector<uint32_t>& freel, uint32_t& used) {
+    if (freel.empty()) return used++;
+    const uint32_t r = freel.back();
+    freel.pop_back();
+    return r;
+}
 // Assigns the rows of one tick's editing buckets (bk: the bucket's index in d_ids); the documents that
 // get no row halt in the kernel with MT_DERR_CAPACITY (mt_apply.hip loc_admit)
 static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt, bool big, bool gx, bool wx = false) {
@@ -170,13 +188,7 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
     const uint32_t kb = rb + pool_reserve(e->nbig, e->bigcap, (uint32_t)nb.size() - rb,
                                           [&](uint32_t r) { return grow_big(e, r); });
     for (uint32_t i = 0; i < kb; i++) {
-        uint32_t r;
-        if (i < rb) {
-            r = e->free_big.back();
-            e->free_big.pop_back();
-        } else {
-            r = e->nbig++;
-        }
+        const uint32_t r = take_row(e->free_big, e->nbig);
         const uint32_t d = nb[i];
         const size_t o = (size_t)r * MT_LOC_BIGCAP, s = (size_t)d * MT_LOC_CAP;
         HIP_OK(hipMemcpy(g.gmb + o, g.gm + s, MT_LOC_CAP * 8, hipMemcpyDeviceToDevice));
@@ -190,13 +202,7 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
     const uint32_t kg = rg + pool_reserve(e->ngx, e->gxcap, (uint32_t)ng.size() - rg,
                                           [&](uint32_t r) { return grow_gx(e, r); });
     for (uint32_t i = 0; i < kg; i++) {
-        uint32_t r;
-        if (i < rg) {
-            r = e->free_gx.back();
-            e->free_gx.pop_back();
-        } else {
-            r = e->ngx++;
-        }
+        const uint32_t r = take_row(e->free_gx, e->ngx);
         const uint32_t d = ng[i];
         e->h_locgx[d] = r;
         HIP_OK(hipMemcpy(g.locgx + d, &r, 4, hipMemcpyHostToDevice));
@@ -207,13 +213,7 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
     const uint32_t kw = rw + pool_reserve(e->nwx, e->wxcap, (uint32_t)nw.size() - rw,
                                           [&](uint32_t r) { return grow_wx(e, r); });
     for (uint32_t i = 0; i < kw; i++) {
-        uint32_t r;
-        if (i < rw) {
-            r = e->free_wx.back();
-            e->free_wx.pop_back();
-        } else {
-            r = e->nwx++;
-        }
+        const uint32_t r = take_row(e->free_wx, e->nwx);
         const uint32_t d = nw[i];
         e->h_locwx[d] = r;
         HIP_OK(hipMemcpy(g.locwx + d, &r, 4, hipMemcpyHostToDevice));
@@ -391,6 +391,7 @@ mt_status mt_engine_destroy(mt_engine* e) {
     if (e->g.evn) (void)hipFree(e->g.evn);
     refs_free(e);
     if (e->ws) (void)hipFree(e->ws);
+    if (e->ckpt_cache.dev) (void)hipFree(e->ckpt_cache.dev);
     for (void* p : {(void*)e->g.gmb, (void*)e->g.pkb, (void*)e->g.ctb, (void*)e->g.lsqb, (void*)e->g.gmx,
                     (void*)e->g.locx, (void*)e->g.pkw})
         if (p) (void)hipFree(p);
@@ -476,14 +477,7 @@ mt_status mt_set_label_keys(mt_engine* e, uint32_t doc, int tile_key, int range_
     for (uint32_t d = d0; d < d1; d++)
         if (merge(e->lkeys[d], keys) == 0xFFFFFFFFu) return MT_ERR_ARG;
     HIP_OK(hipSetDevice(e->cfg.device));
-    if (!e->g.slab) {
-        uint32_t *p = nullptr, *px = nullptr;
-        if (dalloc(e, &p, (size_t)e->cfg.max_docs * e->g.segcap) ||
-            dalloc(e, &px, (size_t)e->cfg.max_docs * e->g.segcap))
-            return MT_ERR_NOMEM;
-        e->g.slab = p;
-        e->g.slabx = px;
-    }
+    if (const mt_status ss = ensure_slab(e)) return ss;
     for (uint32_t d = d0; d < d1; d++) e->lkeys[d] = (uint16_t)merge(e->lkeys[d], keys);
     e->gen++;
     HIP_OK(mt_launch_label_keys(&e->g, d0, d1, keys, e->stream));
@@ -537,6 +531,241 @@ mt_status mt_docs_load(mt_engine* e, uint32_t n, const uint32_t* doc_ids, const 
         .launch(mt_launch_refs_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
         .launch(mt_launch_intervals_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
         .sync().status();
+}
+
+// ---- document checkpoints (mt_ckpt.h; the kernels: mt_ckpt.hip) ------------------------------------
+// What save and restore admit today: observer documents, narrow or wide.  An editing client's document,
+// one with declared label keys, with references or with intervals has its sections in the format and
+// in the host checker, but nothing pins its continuation on the device yet: both calls refuse it
+// (MT_ERR_CKPT) rather than park a document that may not come back as it was.
+static bool ckpt_supported(const mt_ckpt_dochdr& h) {
+    return !(h.flags & MT_CKF_LOC) && h.sc.label_keys == MT_NO_LABEL_KEYS && h.n_refs == 0 && h.n_ivs == 0;
+}
+// The sizing half of mt_docs_save: fold the pending event rows of the documents with references (the
+// saved tables are settled), one header per document from the device, the offsets summed in 64 bits.
+static mt_status ckpt_size(mt_engine* e, uint32_t n, const uint32_t* ids) {
+    auto& c = e->ckpt_cache;
+    if (c.valid && c.gen == e->gen && c.ids.size() == n && std::equal(c.ids.begin(), c.ids.end(), ids)) return MT_OK;
+    c.valid = false;
+    if (c.dev) (void)hipFree(c.dev);
+    c.dev = nullptr;
+    mt_layout l;
+    const size_t o_ids = l.add<uint32_t>(n);
+    c.o_hdr = l.add<mt_ckpt_dochdr>(n);
+    c.o_off = l.add<uint64_t>(n);
+    if (l.bad || hipMalloc(&c.dev, l.total ? l.total : 1) != hipSuccess) {
+        c.dev = nullptr;
+        return MT_ERR_NOMEM;
+    }
+    uint8_t* dev = static_cast<uint8_t*>(c.dev);
+    auto* d_ids = reinterpret_cast<uint32_t*>(dev + o_ids);
+    auto* d_hdr = reinterpret_cast<mt_ckpt_dochdr*>(dev + c.o_hdr);
+    std::vector<mt_ckpt_dochdr> hdr(n);
+    const mt_status st = mt_chain(e->stream)
+                             .launch(mt_launch_refs_track, &e->g, e->n_docs, e->stream)
+                             .h2d(d_ids, ids, n * sizeof(uint32_t))
+                             .launch(mt_launch_ckpt_size, &e->g, d_ids, n, d_hdr, e->stream)
+                             .d2h(hdr.data(), d_hdr, n * sizeof(mt_ckpt_dochdr))
+                             .sync().status();
+    if (st) return st;
+    std::vector<uint64_t> off(n);
+    uint64_t at = mt_ckpt_front(n);
+    c.max_doc = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t b = mt_ckpt_doc_bytes(hdr[i]);
+        off[i] = at;
+        at += b;
+        c.max_doc = std::max(c.max_doc, b);
+    }
+    if (n) HIP_OK(hipMemcpy(dev + c.o_off, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    c.unsupported = false;
+    for (uint32_t i = 0; i < n; i++) c.unsupported = c.unsupported || !ckpt_supported(hdr[i]);
+    c.total = at;
+    c.ids.assign(ids, ids + n);
+    c.gen = e->gen;
+    c.valid = true;
+    return MT_OK;
+}
+// workgroups per document of a pack / unpack launch: one per 64 KiB of the largest document
+static uint32_t ckpt_parts(uint64_t max_doc) {
+    return (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, max_doc >> 16));
+}
+
+mt_status mt_docs_save(mt_engine* e, uint32_t n, const uint32_t* doc_ids, uint8_t* buf, uint64_t cap, uint64_t* bytes) {
+    if (!e || !bytes || n > e->n_docs) return MT_ERR_ARG;
+    std::vector<uint32_t> all;
+    if (!doc_ids) {
+        all.resize(n);
+        for (uint32_t i = 0; i < n; i++) all[i] = i;
+        doc_ids = all.data();
+    }
+    if (!mt_docs_below(doc_ids, n, e->n_docs)) return MT_ERR_ARG;
+    HIP_OK(hipSetDevice(e->cfg.device));
+    if (const mt_status st = ckpt_size(e, n, doc_ids)) return st;
+    auto& c = e->ckpt_cache;
+    *bytes = c.total;
+    if (c.unsupported) return MT_ERR_CKPT;
+    if (!buf) return MT_OK;
+    if (cap < c.total) return MT_ERR_ARG;
+    // the documents packed at their blob offsets in one staging buffer, one copy back, then the header,
+    // the directory and the digest on the host
+    const uint64_t front = mt_ckpt_front(n);
+    uint8_t* dev = static_cast<uint8_t*>(c.dev);
+    void* stage = nullptr;
+    if (hipMalloc(&stage, c.total) != hipSuccess) return MT_ERR_NOMEM;
+    std::vector<mt_ckpt_dochdr> hdr(n);
+    const mt_status st =
+        mt_chain(e->stream)
+            .launch(hipMemsetAsync, stage, 0, c.total, e->stream)  // (no byte of the blob is left as allocated)
+            .launch(hipEventRecord, e->ev0, e->stream)
+            .launch(mt_launch_ckpt_pack, &e->g, reinterpret_cast<const uint32_t*>(dev), n,
+                    reinterpret_cast<const mt_ckpt_dochdr*>(dev + c.o_hdr), reinterpret_cast<const uint64_t*>(dev + c.o_off),
+                    static_cast<uint8_t*>(stage), ckpt_parts(c.max_doc), e->stream)
+            .launch(hipEventRecord, e->ev1, e->stream)
+            .d2h(buf + front, static_cast<uint8_t*>(stage) + front, c.total - front)
+            .d2h(hdr.data(), dev + c.o_hdr, n * sizeof(mt_ckpt_dochdr))
+            .sync().status();
+    (void)hipFree(stage);
+    if (st) return st;
+    HIP_OK(hipEventElapsedTime(&e->ckpt_pack_ms, e->ev0, e->ev1));
+    e->ckpt_pack_bytes = c.total - front;
+    std::vector<uint64_t> sz(n);
+    for (uint32_t i = 0; i < n; i++) sz[i] = mt_ckpt_doc_bytes(hdr[i]);
+    mt_ckpt_write_front(buf, n, sz.data());
+    return MT_OK;
+}
+
+mt_status mt_checkpoint_check(const uint8_t* blob, uint64_t bytes, uint32_t* n_docs, uint32_t* bad, uint32_t* why) {
+    uint32_t b = 0xFFFFFFFFu, nd = 0;
+    const uint32_t w = mt_ckpt_check(blob, bytes, &nd, &b);
+    if (n_docs) *n_docs = nd;
+    if (bad) *bad = b;
+    if (why) *why = w;
+    return w ? MT_ERR_CKPT : MT_OK;
+}
+
+mt_status mt_checkpoint_doc(const uint8_t* blob, uint64_t bytes, uint32_t i, mt_ckpt_doc* out) {
+    mt_ckpt_header bh;
+    if (!out) return MT_ERR_ARG;
+    if (mt_ckpt_check_front(blob, bytes, &bh)) return MT_ERR_CKPT;
+    if (i >= bh.n_docs) return MT_ERR_ARG;
+    const mt_ckpt_dirent de = mt_ckpt_dir(blob, i);
+    if (mt_ckpt_check_doc(blob + de.off, de.bytes)) return MT_ERR_CKPT;
+    mt_ckpt_dochdr h;
+    memcpy(&h, blob + de.off, sizeof h);
+    mt_ckpt_doc o{};
+    o.nseg = mt_ckpt_nseg(h);
+    o.text_units = h.sc.text_top;
+    o.class_bits = ((h.sc.wide & MT_WIDE_DOC) ? MT_CLASS_WIDE : 0u) | ((h.flags & MT_CKF_LOC) ? MT_CLASS_EDITING : 0u) |
+                   ((h.sc.wide & MT_WIDE_GROUPS) ? MT_CLASS_GROUPS : 0u) | ((h.sc.wide & MT_WIDE_LDS) ? MT_CLASS_LDS : 0u) |
+                   ((h.sc.wide & MT_WIDE_C64) ? MT_CLASS_C64 : 0u);
+    o.intervals = h.n_ivs;
+    o.err = h.sc.err;
+    o.bytes = de.bytes;
+    mt_ckpt_walk(h, [&](int id, uint64_t off, uint64_t b) {
+        const uint8_t* p = blob + de.off + off;
+        if (id == CK_LOC && b) {
+            mt_loc lc;
+            memcpy(&lc, p, sizeof lc);
+            o.pending = lc.ghi - lc.glo;
+        } else if (id == CK_REFIDX) {
+            for (uint32_t k = 0; k < h.n_refs; k++) {
+                uint32_t x;
+                memcpy(&x, p + 4ull * k, 4);
+                o.refs += !(x & MT_CKPT_GHOST);
+            }
+        }
+    });
+    *out = o;
+    return MT_OK;
+}
+
+mt_status mt_docs_restore(mt_engine* e, const uint8_t* blob, uint64_t bytes, uint32_t n, const uint32_t* src,
+                          const uint32_t* doc_ids, uint32_t* bad) {
+    if (bad) *bad = 0xFFFFFFFFu;
+    if (!e || !blob || (n && !doc_ids)) return MT_ERR_ARG;
+    uint32_t nd = 0, b = 0;
+    if (mt_ckpt_check(blob, bytes, &nd, &b)) {  // (nothing of a blob that fails goes any further)
+        if (bad) *bad = b;
+        return MT_ERR_CKPT;
+    }
+    if (n == 0) return MT_OK;
+    const mt_gstate& g = e->g;
+    std::vector<uint8_t> seen(e->n_docs, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        if ((src ? src[i] : i) >= nd || doc_ids[i] >= e->n_docs || seen[doc_ids[i]]) return MT_ERR_ARG;
+        seen[doc_ids[i]] = 1;
+    }
+    // every document against this engine's capacities
+    bool wide = false;
+    uint64_t max_doc = 0;
+    std::vector<mt_ckpt_dochdr> hdr(n);
+    std::vector<mt_ckpt_dirent> dir(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t s = src ? src[i] : i;
+        dir[i] = mt_ckpt_dir(blob, s);
+        mt_ckpt_dochdr& h = hdr[i];
+        memcpy(&h, blob + dir[i].off, sizeof h);
+        const mt_doc_scalars& sc = h.sc;
+        const bool w = (sc.wide & MT_WIDE_DOC) != 0;
+        bool fits = (uint32_t)sc.nseg <= g.segcap && (uint32_t)sc.nb[0] <= g.lbcap && (uint32_t)sc.heap_n < g.hcap &&
+                    (uint64_t)sc.text_top * (w ? 2u : 1u) <= g.textcap;
+        for (int l = 1; l < sc.nlev; l++) fits = fits && (uint32_t)sc.nb[l] <= g.ibcap;
+        if ((h.flags & MT_CKF_LOC) && sc.nseg > MT_LOC_BIGCAP) fits = false;
+        if (!fits || !ckpt_supported(h)) {
+            if (bad) *bad = s;
+            return MT_ERR_CKPT;
+        }
+        wide = wide || w;
+        max_doc = std::max(max_doc, dir[i].bytes);
+    }
+    HIP_OK(hipSetDevice(e->cfg.device));
+    // what can fail for want of memory comes before a slot is touched: the wide arrays, the staging buffer
+    if (wide)
+        if (const mt_status st = ensure_wide(e)) return st;
+    // staging: the documents back to back (runs of neighbours in the blob: one copy each)
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        off[i] = total;
+        total += dir[i].bytes;
+    }
+    mt_scratch scr;
+    auto [d_ids, d_off, d_in] = scr.carve<uint32_t, uint64_t, uint8_t>(n, n, total);
+    if (scr.status()) return scr.status();
+    // the slots start over as in mt_docs_load: pool rows given back, no label keys
+    if (const mt_status rs = release_loc_rows(e, doc_ids, n)) return rs;
+    if (e->lkeys.size() < e->cfg.max_docs) e->lkeys.resize(e->cfg.max_docs, (uint16_t)MT_NO_LABEL_KEYS);
+    for (uint32_t i = 0; i < n; i++) e->lkeys[doc_ids[i]] = (uint16_t)MT_NO_LABEL_KEYS;
+    e->gen++;
+    mt_chain ch(e->stream);
+    ch.h2d(d_ids, doc_ids, n * sizeof(uint32_t)).h2d(d_off, off.data(), n * sizeof(uint64_t));
+    for (uint32_t i = 0; i < n;) {
+        uint32_t j = i + 1;
+        while (j < n && dir[j].off == dir[j - 1].off + dir[j - 1].bytes) j++;
+        ch.h2d(d_in + off[i], blob + dir[i].off, off[j - 1] + dir[j - 1].bytes - off[i]);
+        i = j;
+    }
+    ch.launch(mt_launch_refs_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
+        .launch(mt_launch_intervals_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
+        .launch(hipEventRecord, e->ev0, e->stream)
+        .launch(mt_launch_ckpt_unpack, &e->g, d_ids, n, d_off, d_in, ckpt_parts(max_doc), e->stream)
+        .launch(hipEventRecord, e->ev1, e->stream)
+        .sync();
+    if (ch.status()) return ch.status();
+    HIP_OK(hipEventElapsedTime(&e->ckpt_unpack_ms, e->ev0, e->ev1));
+    e->ckpt_unpack_bytes = total;
+    return MT_OK;
+}
+
+mt_status mt_last_checkpoint_stats(mt_engine* e, float* pack_ms, uint64_t* pack_bytes, float* unpack_ms,
+                                   uint64_t* unpack_bytes) {
+    if (!e) return MT_ERR_ARG;
+    if (pack_ms) *pack_ms = e->ckpt_pack_ms;
+    if (pack_bytes) *pack_bytes = e->ckpt_pack_bytes;
+    if (unpack_ms) *unpack_ms = e->ckpt_unpack_ms;
+    if (unpack_bytes) *unpack_bytes = e->ckpt_unpack_bytes;
+    return MT_OK;
 }
 
 mt_status mt_batch_upload(mt_engine* e, const mt_op_rec* ops, uint64_t n_ops, const uint8_t* payload,

@@ -119,6 +119,17 @@ struct mt_engine {
         std::string json;
         std::vector<uint64_t> off;
     } snap_cache;
+    struct {  // mt_docs_save: the sizing of the last call (the documents, their headers and offsets on the device)
+        bool valid = false;
+        uint64_t gen = 0, total = 0, max_doc = 0;
+        std::vector<uint32_t> ids;
+        void* dev = nullptr;  // one allocation: ids, headers, offsets
+        size_t o_hdr = 0, o_off = 0;
+        bool unsupported = false;  // a document save refuses (mt_engine.cpp ckpt_supported)
+    } ckpt_cache;
+    // mt_last_checkpoint_stats: the last pack / unpack launch by HIP events, and the blob bytes it moved
+    float ckpt_pack_ms = 0.f, ckpt_unpack_ms = 0.f;
+    uint64_t ckpt_pack_bytes = 0, ckpt_unpack_bytes = 0;
 };
 
 #define HIP_OK(x)                                                                                            \

@@ -102,6 +102,17 @@ hipError_t mt_launch_intervals_free_docs(const mt_gstate* g, const uint32_t* ids
 hipError_t mt_launch_intervals_gather(const mt_gstate* g, const uint32_t* docs, uint32_t n, uint32_t n_docs,
                                       mt_interval_pos* out, hipStream_t st);
 
+// ---- mt_ckpt.hip: document checkpoints (mt_ckpt.h)
+// hdr[i] = the checkpoint header of document ids[i] (sizes follow from it: mt_ckpt_walk)
+hipError_t mt_launch_ckpt_size(const mt_gstate* g, const uint32_t* ids, uint32_t n, struct mt_ckpt_dochdr* hdr,
+                               hipStream_t st);
+// document ids[i] packed at out + off[i] (hdr: the sizing launch's); parts: workgroups per document
+hipError_t mt_launch_ckpt_pack(const mt_gstate* g, const uint32_t* ids, uint32_t n, const struct mt_ckpt_dochdr* hdr,
+                               const uint64_t* off, uint8_t* out, uint32_t parts, hipStream_t st);
+// the (checked) document at in + off[i] into slot ids[i]
+hipError_t mt_launch_ckpt_unpack(const mt_gstate* g, const uint32_t* ids, uint32_t n, const uint64_t* off,
+                                 const uint8_t* in, uint32_t parts, hipStream_t st);
+
 // ---- mt_text.hip: text reads
 hipError_t mt_launch_text_ranges(const mt_gstate* g, const mt_text_query* q, uint32_t n, uint32_t n_docs,
                                  const uint32_t* row_ptr, uint16_t* units, const uint32_t* m_row_ptr,

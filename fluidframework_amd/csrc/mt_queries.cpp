@@ -128,6 +128,7 @@ mt_status mt_regen_drain(mt_engine* e, uint32_t doc, mt_op_rec* recs, uint32_t c
         HIP_OK(hipMemcpy(recs, e->g.rg + (size_t)doc * MT_RG_RECS, cnt[0] * sizeof(mt_op_rec), hipMemcpyDeviceToHost));
     if (cnt[1]) HIP_OK(hipMemcpy(payload, e->g.rgp + (size_t)doc * MT_RG_BYTES, cnt[1], hipMemcpyDeviceToHost));
     HIP_OK(hipMemset(&e->g.loc[doc].rgn, 0, sizeof cnt));
+    e->gen++;  // (the regenerated ops are document state: mt_docs_save)
     return MT_OK;
 }
 
@@ -259,6 +260,7 @@ mt_status mt_refs_remove(mt_engine* e, const uint32_t* docs, const uint32_t* han
     HIP_OK(hipSetDevice(e->cfg.device));
     HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
     if (n == 0) return MT_OK;
+    e->gen++;
     mt_scratch s;
     auto [dd, dh] = s.carve<uint32_t, uint32_t>(n, n);
     return mt_chain(e->stream, s.status())
@@ -387,6 +389,7 @@ mt_status mt_intervals_remove(mt_engine* e, const mt_interval_query* q, uint32_t
     HIP_OK(hipSetDevice(e->cfg.device));
     HIP_OK(mt_launch_refs_track(&e->g, e->n_docs, e->stream));
     if (n == 0) return MT_OK;
+    e->gen++;
     mt_scratch s;
     auto [dq, dh] = s.carve<mt_interval_query, uint32_t>(n, n);
     return mt_chain(e->stream, s.status())

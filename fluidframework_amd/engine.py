@@ -16,7 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MTGPU_LIB') or os.path.join(HERE, 'libmtgpu.so')
 
 MT_ERRORS = {0: 'ok', 1: 'bad argument', 2: 'HIP error', 3: 'out of device memory', 4: 'bad state',
-             5: 'document error', 6: 'RCCL error', 7: 'document past the form of the call (wide)'}
+             5: 'document error', 6: 'RCCL error', 7: 'document past the form of the call (wide)',
+             8: 'checkpoint malformed, or too large for the engine'}
 DOC_ERRORS = {0: None,
               1: "Incoming remote op sequence# <= local collabWindow's currentSequence#",
               2: "Incoming remote op minSequence# < local collabWindow's minSequence#",
@@ -50,6 +51,18 @@ STACK_ITEM_DTYPE = np.dtype([('pos', '<i4'), ('ordinal', '<i4'), ('ref_type', '<
 
 class MtError(RuntimeError):
     pass
+
+
+MT_ERR_CKPT = 8
+
+
+class CheckpointError(MtError):
+    """MT_ERR_CKPT: .bad = the blob's document (0xFFFFFFFF: its header), .why = mt_ckpt_why (0 when the
+    blob itself is good and the document does not fit the engine)."""
+
+    def __init__(self, msg, bad, why=0):
+        super().__init__(msg)
+        self.bad, self.why = bad, why
 
 
 class _Cfg(ctypes.Structure):
@@ -118,6 +131,15 @@ def lib():
         L.mt_events_enable.argtypes = [vp, u32]
         L.mt_events_drain.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64)]
         L.mt_set_label_keys.argtypes = [vp, u32, i32, i32]
+        L.mt_docs_save.argtypes = [vp, u32, vp, vp, u64, ctypes.POINTER(u64)]
+        L.mt_docs_restore.argtypes = [vp, vp, u64, u32, vp, vp, ctypes.POINTER(u32)]
+        L.mt_checkpoint_check.argtypes = [vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.mt_checkpoint_doc.argtypes = [vp, u64, u32, vp]
+        L.mt_last_checkpoint_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(u64),
+                                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(u64)]
+        for name in ('mt_docs_save', 'mt_docs_restore', 'mt_checkpoint_check', 'mt_checkpoint_doc',
+                     'mt_last_checkpoint_stats'):
+            getattr(L, name).restype = ctypes.c_int
         for name, at in (('mt_refs_enable', [vp, u32]), ('mt_refs_add', [vp, vp, u32, vp]),
                          ('mt_refs_remove', [vp, vp, vp, u32]), ('mt_refs_positions', [vp, vp, vp, u32, vp]),
                          ('mt_refs_positions_device', [vp, vp, vp, u32, vp]), ('mt_refs_dropped', [vp, vp, u32]),
@@ -595,6 +617,56 @@ class MergeEngine:
         _check(lib().mt_sync(self.h), 'mt_sync')
 
     # -- readout -------------------------------------------------------------------------
+    # -- checkpoints (include/mtgpu.h "document checkpoints") --------------------------------
+    def save_docs(self, docs=None):
+        """The exact device state of documents `docs` (default: all) as one self-describing blob
+        (uint8 array): restore_docs puts them into any slots of any engine that holds them, and they
+        go on bit-exactly.  Observer documents only, today: an editing client's document, or one with
+        label keys, references or intervals, raises CheckpointError.  Events not drained yet are not
+        part of it: drain them first."""
+        ids = np.arange(self.n_docs, dtype=np.uint32) if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
+        nbytes = ctypes.c_uint64()
+        blob = None
+        for _ in range(2):  # the size, then the blob
+            rc = lib().mt_docs_save(self.h, len(ids), _ptr(ids), None if blob is None else _ptr(blob),
+                                    0 if blob is None else len(blob), ctypes.byref(nbytes))
+            if rc == MT_ERR_CKPT:
+                raise CheckpointError('mt_docs_save: a document is not an observer document '
+                                      '(editing client, label keys, references or intervals)', 0xFFFFFFFF)
+            _check(rc, 'mt_docs_save')
+            if blob is None:
+                blob = np.zeros(nbytes.value, dtype=np.uint8)
+        return blob
+
+    def restore_docs(self, blob, docs=None, src=None):
+        """Documents src[i] of the blob (default: i) into slots docs[i] (default: i); all or nothing.
+        A blob that is malformed, or a document that does not fit this engine or is not an observer
+        document, raises CheckpointError (.bad: the blob's document) and touches no slot."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if src is not None:
+            src = np.ascontiguousarray(src, dtype=np.uint32)
+        if docs is None:
+            # (the header's count; mt_docs_restore checks the whole blob, once)
+            n = len(src) if src is not None else (int(blob[12:16].view('<u4')[0]) if len(blob) >= 32 else 0)
+            docs = np.arange(n, dtype=np.uint32)
+        docs = np.ascontiguousarray(docs, dtype=np.uint32)
+        assert src is None or len(src) == len(docs)
+        bad = ctypes.c_uint32()
+        rc = lib().mt_docs_restore(self.h, _ptr(blob), len(blob), len(docs), None if src is None else _ptr(src),
+                                   _ptr(docs), ctypes.byref(bad))
+        if rc == MT_ERR_CKPT:
+            raise CheckpointError(f'mt_docs_restore: {MT_ERRORS[rc]} (document {bad.value})', bad.value)
+        _check(rc, 'mt_docs_restore')
+        return self
+
+    def checkpoint_stats(self):
+        """(pack_ms, pack_bytes, unpack_ms, unpack_bytes) of the last save_docs / restore_docs: the kernels
+        by HIP events and the blob bytes each moved (it reads and writes that many)."""
+        pm, um, pb, ub = ctypes.c_float(), ctypes.c_float(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mt_last_checkpoint_stats(self.h, ctypes.byref(pm), ctypes.byref(pb), ctypes.byref(um),
+                                              ctypes.byref(ub)), 'mt_last_checkpoint_stats')
+        return pm.value, pb.value, um.value, ub.value
+
     def checksums(self):
         out = np.zeros(self.n_docs, dtype=np.uint64)
         _check(lib().mt_checksums(self.h, _ptr(out), self.n_docs), 'mt_checksums')

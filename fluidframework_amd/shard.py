@@ -41,6 +41,16 @@ def route(doc_ids, n_ranks):
     return (splitmix64(doc_ids) % np.uint64(n_ranks)).astype(np.uint32)
 
 
+def moves(doc_ids, n_old, n_new):
+    """The documents that change rank when the ranks go from n_old to n_new: (ids, from_rank, to_rank),
+    in the order of doc_ids.  Each is saved on from_rank and restored on to_rank
+    (MergeEngine.save_docs / restore_docs); every other document stays where it is."""
+    ids = np.asarray(doc_ids)
+    a, b = route(ids, n_old), route(ids, n_new)
+    m = a != b
+    return ids[m], a[m], b[m]
+
+
 def shard_ids(rank, n_ranks, n_total):
     """Global ids (ascending) of the documents of [0, n_total) that live on `rank`."""
     ids = np.arange(n_total, dtype=np.uint64)

@@ -209,8 +209,10 @@ typedef enum mt_status {
     MT_ERR_STATE = 4,
     MT_ERR_DOC = 5,         /* at least one document has a sticky error (see mt_doc_error) */
     MT_ERR_COMM = 6,        /* an RCCL call failed (mt_comm_*) */
-    MT_ERR_WIDE = 7         /* the call's form cannot express the document (a deli checkpoint of a
+    MT_ERR_WIDE = 7,        /* the call's form cannot express the document (a deli checkpoint of a
                                document past client 63: mt_deli_get_checkpoint_wide) */
+    MT_ERR_CKPT = 8         /* a document checkpoint that is malformed, or that does not fit the engine
+                               (mt_docs_restore, mt_checkpoint_check) */
 } mt_status;
 
 /* per-document sticky error codes (mirror the reference's assert/throw sites) */
@@ -290,6 +292,78 @@ typedef struct mt_load_seg {  /* 96 bytes */
 mt_status mt_docs_load(mt_engine* eng, uint32_t n, const uint32_t* doc_ids, const uint32_t* seg_row_ptr,
                        const mt_load_seg* segs, const uint8_t* text, uint64_t text_bytes, const int32_t* min_seq,
                        const int32_t* cur_seq);
+
+/* ---- document checkpoints (DESIGN.md "Checkpoints") --------------------------------------------
+ * A checkpoint is a self-describing blob of the exact device state of one or more documents: the
+ * scalars (the sticky error too: a halted document stays halted), the segments, the block shape with
+ * every needsScour, the LRU heap and the text.  Unlike a snapshot (mt_get_snapshots + mt_docs_load: a
+ * summary that coalesces and rebuilds the tree) a restored document goes on bit-exactly as the saved
+ * one would have: same states, same checksums, same delta and maintenance callbacks.
+ * The blob names no slot, stride, arena half or pool row: it restores into any slot of any engine
+ * whose capacities hold the document, and saving it again there gives the same bytes.
+ * TODAY both calls admit OBSERVER documents only, narrow or wide.  The format (csrc/mt_ckpt.h, version
+ * 1) and the host checker also cover an editing client's pending state, declared label keys with their
+ * stale block caches, local references and intervals, but a document that has any of them is refused
+ * (MT_ERR_CKPT from mt_docs_save, nothing written; MT_ERR_CKPT from mt_docs_restore, no slot touched)
+ * until its continuation after a restore is pinned by tests on the device.
+ * NOT saved: the delta / maintenance events not drained yet (drain them first: mt_events_drain).
+ *
+ * mt_docs_save: documents doc_ids[0..n) (NULL: 0..n-1) into buf.  Two calls like mt_get_snapshots:
+ * buf == NULL returns the size in *bytes (the sizing is kept until the engine's state changes); with
+ * cap below it: MT_ERR_ARG.  Synchronises. */
+mt_status mt_docs_save(mt_engine* eng, uint32_t n, const uint32_t* doc_ids, uint8_t* buf, uint64_t cap,
+                       uint64_t* bytes);
+/* Document src[i] of the blob (NULL: i) into slot doc_ids[i] (distinct slots), i < n; all or nothing.
+ * The blob is checked on the host first (mt_checkpoint_check) and every document against this
+ * engine's capacities (segments, blocks, heap, text, the editing forms' 8192 slots, reference and
+ * interval handles against the enabled tables) and what the call admits (above): on a failure
+ * MT_ERR_CKPT, *bad = the blob document (may be NULL), and no slot is touched.  No byte of a blob that
+ * fails reaches the device.
+ * The target slots start over as in mt_docs_load (pool rows given back, references and intervals
+ * freed, label keys undeclared, events not drained dropped) and then hold the saved documents. */
+mt_status mt_docs_restore(mt_engine* eng, const uint8_t* blob, uint64_t bytes, uint32_t n, const uint32_t* src,
+                          const uint32_t* doc_ids, uint32_t* bad);
+/* The last mt_docs_save's pack launch and the last mt_docs_restore's unpack launch by HIP events, and
+ * the blob bytes each moved (it reads and writes that many: traffic = 2 x bytes).  Any may be NULL. */
+mt_status mt_last_checkpoint_stats(mt_engine* eng, float* pack_ms, uint64_t* pack_bytes, float* unpack_ms,
+                                   uint64_t* unpack_bytes);
+/* What a blob says of one of its documents */
+typedef struct mt_ckpt_doc {
+    uint32_t nseg;        /* linked segments                                                       */
+    uint32_t text_units;  /* code units in the arena (bytes; a wide document: UTF-16 units)         */
+    uint32_t class_bits;  /* MT_CLASS_WIDE / _EDITING / _GROUPS / _LDS / _C64 as the apply classes read */
+    uint32_t pending;     /* an editing client's pending edits                                     */
+    uint32_t refs;        /* local references (ghosts not counted)                                 */
+    uint32_t intervals;
+    int32_t err;          /* mt_doc_err                                                            */
+    uint32_t pad;
+    uint64_t bytes;       /* of the blob                                                           */
+} mt_ckpt_doc;
+/* Reasons of mt_checkpoint_check (*why) */
+enum mt_ckpt_why {
+    MT_CKW_OK = 0,
+    MT_CKW_TRUNCATED = 1,  /* shorter than its header, directory or total says                      */
+    MT_CKW_MAGIC = 2,
+    MT_CKW_VERSION = 3,
+    MT_CKW_DIRECTORY = 4,  /* an entry out of bounds, unaligned, overlapping or out of order         */
+    MT_CKW_DIGEST = 5,
+    MT_CKW_SIZE = 6,       /* a document's bytes disagree with its scalars                          */
+    MT_CKW_SCALARS = 7,    /* counts out of range (nseg, levels, blocks, heap, window, flags)        */
+    MT_CKW_BLOCKS = 8,     /* child counts: above 8, or a level does not sum to the one below       */
+    MT_CKW_TEXT = 9,       /* a segment's text outside text_top                                     */
+    MT_CKW_HEAP = 10,      /* a heap slot neither a segment nor MT_DEAD_SLOT                        */
+    MT_CKW_IDS = 11,       /* a client id or key id outside the form's limits                       */
+    MT_CKW_PENDING = 12,   /* glo > ghi, more pending edits than the form holds, rgn / rgpn         */
+    MT_CKW_REFS = 13,      /* a reference's ordinal, flags or index                                 */
+    MT_CKW_INTERVALS = 14  /* an interval endpoint that names no stored reference, or its index     */
+};
+/* Host only, no engine, no device.  Checks the header, the directory, the digest, and per document
+ * every invariant a kernel later trusts.  MT_ERR_CKPT: *bad = the document (0xFFFFFFFF: the header),
+ * *why = mt_ckpt_why.  n_docs / bad / why may be NULL.  A large blob is checked on all host cores. */
+mt_status mt_checkpoint_check(const uint8_t* blob, uint64_t bytes, uint32_t* n_docs, uint32_t* bad, uint32_t* why);
+/* Document i of a blob that passes mt_checkpoint_check (header and directory are re-checked; the
+ * digest is not). */
+mt_status mt_checkpoint_doc(const uint8_t* blob, uint64_t bytes, uint32_t i, mt_ckpt_doc* out);
 
 /* Host -> device staging of a CSR op batch.  Ops are grouped by document (doc_row_ptr has
  * n_docs+1 entries) and seq-ascending within a document.  Buffers are caller-owned and copied
