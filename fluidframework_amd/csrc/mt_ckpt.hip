@@ -8,7 +8,8 @@
 // in the blob; where the engine's row does too (the per-segment arrays of an engine whose
 // seg_capacity is a multiple of 16, the text, the pool rows) a lane moves 16 bytes per instruction
 // and only the section's last partial vector goes byte by byte; a row that is not (the heap from
-// entry 1 on, an odd capacity) is copied at the widest unit both sides share.
+// entry 1 on, an odd capacity, an editing document's mt_loc: 540 bytes per slot) is copied at the widest
+// unit both sides share.
 //
 // Workgroup: 256 threads per document, `parts` workgroups per document (grid.y).  A document of a few
 // KB has ~25 short sections and is bound by their latency, not by lanes: the four waves each take a
@@ -52,9 +53,10 @@ __device__ __forceinline__ void ck_copy(uint8_t* __restrict__ dst, const uint8_t
 }
 
 // Where section `id` of the document in slot d lives in the engine (its first byte).  Null: the overlap
-// halves (not one range there), and the sections of the documents the host does not admit yet -- an
-// editing client's state, the label cache, references, intervals (mt_engine.cpp ckpt_supported): they
-// are never copied.  `half`: the arena half the text is read from / written to.
+// halves (not one range there), an editing client's sections (the kernels of their own below: ck_loc_ptr),
+// and the sections of the documents the host does not admit -- the label cache, references, intervals
+// (mt_engine.cpp ckpt_supported): they are never copied.  `half`: the arena half the text is read from /
+// written to.
 __device__ __forceinline__ uint8_t* ck_engine_ptr(const mt_gstate& g, uint32_t d, uint32_t half, int id) {
     const size_t so = (size_t)d * g.segcap;
     auto p = [](auto* q) { return reinterpret_cast<uint8_t*>(q); };
@@ -84,6 +86,42 @@ __device__ __forceinline__ uint8_t* ck_engine_ptr(const mt_gstate& g, uint32_t d
     }
 }
 
+// An editing client's sections (CK_LOC .. CK_RGP) have kernels of their own, launched only when a
+// document of the call carries MT_CKF_LOC: inlined into the walk of the kernels above they cost every
+// observer document registers and time (DESIGN.md "Measurement").
+// The pool rows of the document in slot d (MT_NO_ROW: none): read once per workgroup, before the walk.
+struct CkRows {
+    uint32_t big = MT_NO_ROW, gx = MT_NO_ROW, wx = MT_NO_ROW;
+};
+__device__ __forceinline__ CkRows ck_rows(const mt_gstate& g, uint32_t d, uint32_t flags) {
+    CkRows r;
+    if (flags & MT_CKF_BIG) r.big = g.locbig[d];
+    if (flags & MT_CKF_GX) r.gx = g.locgx[d];
+    if (flags & MT_CKF_WX) r.wx = g.locwx[d];
+    return r;
+}
+// Where editing section `id` of the document in slot d lives (its first byte); null: a pool section of a
+// document that holds no such row.  Its per-segment state lies in its big-pool row when it holds one, else
+// in its own 1024-slot row; the section sizes (mt_ckpt_nloc) never pass the row that the flags name.
+__device__ __forceinline__ uint8_t* ck_loc_ptr(const mt_gstate& g, uint32_t d, int id, uint32_t flags, const CkRows& rows) {
+    auto p = [](auto* q) { return reinterpret_cast<uint8_t*>(q); };
+    const bool big = (flags & MT_CKF_BIG) != 0;
+    const size_t lo = big ? (size_t)rows.big * MT_LOC_BIGCAP : (size_t)d * MT_LOC_CAP;
+    switch (id) {
+        case CK_LOC: return p(g.loc + d);
+        case CK_GM: return big && rows.big == MT_NO_ROW ? nullptr : p((big ? g.gmb : g.gm) + lo);
+        case CK_PK: return big && rows.big == MT_NO_ROW ? nullptr : p((big ? g.pkb : g.pk) + lo);
+        case CK_CT: return big && rows.big == MT_NO_ROW ? nullptr : p((big ? g.ctb : g.ct) + lo);
+        case CK_LSQ: return big && rows.big == MT_NO_ROW ? nullptr : p((big ? g.lsqb : g.lsq) + lo);
+        case CK_GMX: return rows.gx == MT_NO_ROW ? nullptr : p(g.gmx + (size_t)rows.gx * MT_LOC_BIGCAP * MT_LOC_GW);
+        case CK_LOCX: return rows.gx == MT_NO_ROW ? nullptr : p(g.locx + rows.gx);
+        case CK_PKW: return rows.wx == MT_NO_ROW ? nullptr : p(g.pkw + (size_t)rows.wx * MT_LOC_BIGCAP * MT_PKW_WORDS);
+        case CK_RG: return p(g.rg + (size_t)d * MT_RG_RECS);
+        case CK_RGP: return g.rgp + (size_t)d * MT_RG_BYTES;
+        default: return nullptr;
+    }
+}
+
 // The checkpoint header of the document in slot d as it stands: what decides every section's size.
 // Called by every lane of one wave (the table counts are wave sums).
 __device__ __forceinline__ mt_ckpt_dochdr ck_header(const mt_gstate& g, uint32_t d, int lane) {
@@ -99,8 +137,14 @@ __device__ __forceinline__ mt_ckpt_dochdr ck_header(const mt_gstate& g, uint32_t
     h.sc.text_top = min(h.sc.text_top, (h.sc.wide & MT_WIDE_DOC) ? g.textcap / 2 : g.textcap);
     const mt_loc& lc = g.loc[d];
     if (lc.own >= 0) {
-        h.flags = MT_CKF_LOC | (g.locbig[d] != MT_NO_ROW ? MT_CKF_BIG : 0u) | (g.locgx[d] != MT_NO_ROW ? MT_CKF_GX : 0u) |
-                  (g.locwx[d] != MT_NO_ROW ? MT_CKF_WX : 0u);
+        // (a group row of a document that is not MT_WIDE_GROUPS, or a wide row of a narrow one, was never stored
+        // into -- the document halted in the launch that was to take it there -- and is not read by its next
+        // load either (mt_apply.hip load): it is not part of its state.  A wide document that halted in the very
+        // launch that gave it its wide row saves that row as the pool held it: bytes of a halted document that
+        // nothing reads, and the same bytes again after a restore.)
+        h.flags = MT_CKF_LOC | (g.locbig[d] != MT_NO_ROW ? MT_CKF_BIG : 0u) |
+                  (g.locgx[d] != MT_NO_ROW && (h.sc.wide & MT_WIDE_GROUPS) ? MT_CKF_GX : 0u) |
+                  (g.locwx[d] != MT_NO_ROW && (h.sc.wide & MT_WIDE_DOC) ? MT_CKF_WX : 0u);
         h.rgn = min(lc.rgn, (uint32_t)MT_RG_RECS);
         h.rgpn = min(lc.rgpn, (uint32_t)MT_RG_BYTES);
     }
@@ -190,8 +234,13 @@ __global__ __launch_bounds__(256) void mt_ckpt_unpack_kernel(mt_gstate g, const 
         static_assert(sizeof(mt_doc_scalars) % 16 == 0, "mt_doc_scalars in 16-byte vectors");
         for (uint32_t q = 0; q < sizeof(mt_doc_scalars) / 16; q++)
             reinterpret_cast<uint4*>(g.sc + d)[q] = reinterpret_cast<const uint4*>(doc)[q];
-        g.loc[d].own = -1;  // an observer, as mt_init_kernel leaves it
-        g.loc[d].glo = g.loc[d].ghi = g.loc[d].stamp = g.loc[d].lseq = g.loc[d].rgn = g.loc[d].rgpn = 0;
+        // An editing client's mt_loc comes with its other sections (mt_ckpt_unpack_loc_kernel, CK_LOC): from
+        // the blob's bytes like the scalars, for the same reason.  Any other document is an observer, as
+        // mt_init_kernel leaves it.
+        if (!(h.flags & MT_CKF_LOC)) {
+            g.loc[d].own = -1;
+            g.loc[d].glo = g.loc[d].ghi = g.loc[d].stamp = g.loc[d].lseq = g.loc[d].rgn = g.loc[d].rgpn = 0;
+        }
         if (g.evn) g.evn[d] = 0;  // events not drained are not part of a checkpoint
         if (g.refs) {
             g.refcur[d] = 0;
@@ -201,6 +250,43 @@ __global__ __launch_bounds__(256) void mt_ckpt_unpack_kernel(mt_gstate g, const 
         }
         if (g.ivs) g.ivn[d] = 0;
     }
+}
+
+// The editing sections of the documents that carry MT_CKF_LOC, same grid as the kernels above (a workgroup
+// of any other document returns at once).  Pack: the padding was zeroed by mt_ckpt_pack_kernel.  Unpack:
+// the host gave the slot one row of each pool its blob's flags name before the launch (locbig / locgx /
+// locwx: read here, never written); a section is at most mt_ckpt_nloc entries, the slots of the row it
+// lands in, and one whose row is missing is skipped.
+__global__ __launch_bounds__(256) void mt_ckpt_pack_loc_kernel(mt_gstate g, const uint32_t* __restrict__ ids, uint32_t n,
+                                                               const mt_ckpt_dochdr* __restrict__ hdr,
+                                                               const uint64_t* __restrict__ off, uint8_t* __restrict__ out) {
+    const uint32_t w = blockIdx.x;
+    if (w >= n || !(hdr[w].flags & MT_CKF_LOC)) return;
+    const uint32_t d = ids[w];
+    const uint32_t tid = blockIdx.y * kCkThreads + threadIdx.x, nth = gridDim.y * kCkThreads;
+    const mt_ckpt_dochdr h = hdr[w];
+    uint8_t* __restrict__ doc = out + off[w];
+    const CkRows rows = ck_rows(g, d, h.flags);
+    mt_ckpt_walk(h, [&](int id, uint64_t o, uint64_t b) {
+        if (id < CK_LOC || id > CK_RGP || b == 0) return;
+        if (uint8_t* src = ck_loc_ptr(g, d, id, h.flags, rows)) ck_copy(doc + o, src, b, tid, nth);
+    });
+}
+__global__ __launch_bounds__(256) void mt_ckpt_unpack_loc_kernel(mt_gstate g, const uint32_t* __restrict__ ids, uint32_t n,
+                                                                 const uint64_t* __restrict__ off,
+                                                                 const uint8_t* __restrict__ in) {
+    const uint32_t w = blockIdx.x;
+    if (w >= n) return;
+    const uint8_t* __restrict__ doc = in + off[w];
+    const mt_ckpt_dochdr h = *reinterpret_cast<const mt_ckpt_dochdr*>(doc);
+    if (!(h.flags & MT_CKF_LOC)) return;
+    const uint32_t d = ids[w];
+    const uint32_t tid = blockIdx.y * kCkThreads + threadIdx.x, nth = gridDim.y * kCkThreads;
+    const CkRows rows = ck_rows(g, d, h.flags);
+    mt_ckpt_walk(h, [&](int id, uint64_t o, uint64_t b) {
+        if (id < CK_LOC || id > CK_RGP || b == 0) return;
+        if (uint8_t* dst = ck_loc_ptr(g, d, id, h.flags, rows)) ck_copy(dst, doc + o, b, tid, nth);
+    });
 }
 
 extern "C" hipError_t mt_launch_ckpt_size(const mt_gstate* g, const uint32_t* ids, uint32_t n, mt_ckpt_dochdr* hdr,
@@ -219,5 +305,17 @@ extern "C" hipError_t mt_launch_ckpt_unpack(const mt_gstate* g, const uint32_t* 
                                             const uint8_t* in, uint32_t parts, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(mt_ckpt_unpack_kernel, dim3(n, parts ? parts : 1), dim3(kCkThreads), 0, st, *g, ids, n, off, in);
+    return hipGetLastError();
+}
+extern "C" hipError_t mt_launch_ckpt_pack_loc(const mt_gstate* g, const uint32_t* ids, uint32_t n, const mt_ckpt_dochdr* hdr,
+                                              const uint64_t* off, uint8_t* out, uint32_t parts, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mt_ckpt_pack_loc_kernel, dim3(n, parts ? parts : 1), dim3(kCkThreads), 0, st, *g, ids, n, hdr, off, out);
+    return hipGetLastError();
+}
+extern "C" hipError_t mt_launch_ckpt_unpack_loc(const mt_gstate* g, const uint32_t* ids, uint32_t n, const uint64_t* off,
+                                                const uint8_t* in, uint32_t parts, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mt_ckpt_unpack_loc_kernel, dim3(n, parts ? parts : 1), dim3(kCkThreads), 0, st, *g, ids, n, off, in);
     return hipGetLastError();
 }

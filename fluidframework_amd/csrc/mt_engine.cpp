@@ -11,6 +11,7 @@
 // are in mt_queries.cpp, the canonical readout in mt_readout.cpp; what the three share is in
 // mt_engine_impl.h.
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -225,27 +226,40 @@ static mt_status assign_loc_rows(mt_engine* e, const uint32_t* ids, uint32_t cnt
 // such a form reuses them before the pools grow (its 1024-slot row is copied in then, as for a new
 // row).  The host mirrors are updated per document; the device tables get one copy of the changed
 // span each and one synchronization (not two round trips per document).
+// The three pools as release_loc_rows and mt_docs_restore see them: the checkpoint flag that names a row
+// of the pool, the host copy of its per-document table, its free list, its rows handed out so far, and
+// the device table.
+struct LocPool {
+    uint32_t flag;
+    std::vector<uint32_t>* mirror;
+    std::vector<uint32_t>* freel;
+    uint32_t* used;
+    uint32_t* dev;
+};
+static std::array<LocPool, 3> loc_pools(mt_engine* e) {
+    return {{{MT_CKF_BIG, &e->h_locbig, &e->free_big, &e->nbig, e->g.locbig},
+             {MT_CKF_GX, &e->h_locgx, &e->free_gx, &e->ngx, e->g.locgx},
+             {MT_CKF_WX, &e->h_locwx, &e->free_wx, &e->nwx, e->g.locwx}}};
+}
+// the span [lo, hi) of a pool's device table from its host copy (queued on the engine stream)
+static mt_status push_loc_table(mt_engine* e, const LocPool& p, uint32_t lo, uint32_t hi) {
+    HIP_OK(hipMemcpyAsync(p.dev + lo, p.mirror->data() + lo, 4ull * (hi - lo), hipMemcpyHostToDevice, e->stream));
+    return MT_OK;
+}
 static mt_status release_loc_rows(mt_engine* e, const uint32_t* docs, uint32_t n) {
-    constexpr int P = 3;  // the pools
-    uint32_t lo[P] = {UINT32_MAX, UINT32_MAX, UINT32_MAX}, hi[P] = {0, 0, 0};
-    std::vector<uint32_t>* mirror[P] = {&e->h_locbig, &e->h_locgx, &e->h_locwx};
-    std::vector<uint32_t>* freel[P] = {&e->free_big, &e->free_gx, &e->free_wx};
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t d = docs[i];
-        for (int k = 0; k < P; k++) {
-            if (d >= mirror[k]->size() || (*mirror[k])[d] == MT_NO_ROW) continue;
-            freel[k]->push_back((*mirror[k])[d]);
-            (*mirror[k])[d] = MT_NO_ROW;
-            lo[k] = std::min(lo[k], d);
-            hi[k] = std::max(hi[k], d + 1);
-        }
-    }
-    uint32_t* dev[P] = {e->g.locbig, e->g.locgx, e->g.locwx};
     bool any = false;
-    for (int k = 0; k < P; k++) {
-        if (lo[k] >= hi[k]) continue;
-        HIP_OK(hipMemcpyAsync(dev[k] + lo[k], mirror[k]->data() + lo[k], 4ull * (hi[k] - lo[k]), hipMemcpyHostToDevice,
-                              e->stream));
+    for (const LocPool& p : loc_pools(e)) {
+        uint32_t lo = UINT32_MAX, hi = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t d = docs[i];
+            if (d >= p.mirror->size() || (*p.mirror)[d] == MT_NO_ROW) continue;
+            p.freel->push_back((*p.mirror)[d]);
+            (*p.mirror)[d] = MT_NO_ROW;
+            lo = std::min(lo, d);
+            hi = std::max(hi, d + 1);
+        }
+        if (lo >= hi) continue;
+        if (const mt_status st = push_loc_table(e, p, lo, hi)) return st;
         any = true;
     }
     if (any) HIP_OK(hipStreamSynchronize(e->stream));
@@ -534,12 +548,13 @@ mt_status mt_docs_load(mt_engine* e, uint32_t n, const uint32_t* doc_ids, const 
 }
 
 // ---- document checkpoints (mt_ckpt.h; the kernels: mt_ckpt.hip) ------------------------------------
-// What save and restore admit today: observer documents, narrow or wide.  An editing client's document,
-// one with declared label keys, with references or with intervals has its sections in the format and
-// in the host checker, but nothing pins its continuation on the device yet: both calls refuse it
-// (MT_ERR_CKPT) rather than park a document that may not come back as it was.
+// What save and restore admit today: observer documents and editing clients' documents (edits pending,
+// regenerated ops not drained, in every editing form), narrow or wide.  A document with declared label
+// keys, with references or with intervals has its sections in the format and in the host checker, but
+// nothing pins its continuation on the device yet: both calls refuse it (MT_ERR_CKPT) rather than park
+// a document that may not come back as it was.
 static bool ckpt_supported(const mt_ckpt_dochdr& h) {
-    return !(h.flags & MT_CKF_LOC) && h.sc.label_keys == MT_NO_LABEL_KEYS && h.n_refs == 0 && h.n_ivs == 0;
+    return h.sc.label_keys == MT_NO_LABEL_KEYS && h.n_refs == 0 && h.n_ivs == 0;
 }
 // The sizing half of mt_docs_save: fold the pending event rows of the documents with references (the
 // saved tables are settled), one header per document from the device, the offsets summed in 64 bits.
@@ -579,7 +594,11 @@ static mt_status ckpt_size(mt_engine* e, uint32_t n, const uint32_t* ids) {
     }
     if (n) HIP_OK(hipMemcpy(dev + c.o_off, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
     c.unsupported = false;
-    for (uint32_t i = 0; i < n; i++) c.unsupported = c.unsupported || !ckpt_supported(hdr[i]);
+    c.any_loc = false;
+    for (uint32_t i = 0; i < n; i++) {
+        c.unsupported = c.unsupported || !ckpt_supported(hdr[i]);
+        c.any_loc = c.any_loc || (hdr[i].flags & MT_CKF_LOC);
+    }
     c.total = at;
     c.ids.assign(ids, ids + n);
     c.gen = e->gen;
@@ -619,6 +638,9 @@ mt_status mt_docs_save(mt_engine* e, uint32_t n, const uint32_t* doc_ids, uint8_
             .launch(hipMemsetAsync, stage, 0, c.total, e->stream)  // (no byte of the blob is left as allocated)
             .launch(hipEventRecord, e->ev0, e->stream)
             .launch(mt_launch_ckpt_pack, &e->g, reinterpret_cast<const uint32_t*>(dev), n,
+                    reinterpret_cast<const mt_ckpt_dochdr*>(dev + c.o_hdr), reinterpret_cast<const uint64_t*>(dev + c.o_off),
+                    static_cast<uint8_t*>(stage), ckpt_parts(c.max_doc), e->stream)
+            .launch(mt_launch_ckpt_pack_loc, &e->g, reinterpret_cast<const uint32_t*>(dev), c.any_loc ? n : 0u,
                     reinterpret_cast<const mt_ckpt_dochdr*>(dev + c.o_hdr), reinterpret_cast<const uint64_t*>(dev + c.o_off),
                     static_cast<uint8_t*>(stage), ckpt_parts(c.max_doc), e->stream)
             .launch(hipEventRecord, e->ev1, e->stream)
@@ -733,8 +755,52 @@ mt_status mt_docs_restore(mt_engine* e, const uint8_t* blob, uint64_t bytes, uin
     mt_scratch scr;
     auto [d_ids, d_off, d_in] = scr.carve<uint32_t, uint64_t, uint8_t>(n, n, total);
     if (scr.status()) return scr.status();
+    // ... and the editing documents' pools: one row per restored document whose flags name one, out of the
+    // rows given back before, the rows the target slots give back below, and else a pool grown here
+    // (No slot is touched when a pool cannot grow; a pool grown before another fails stays grown.)
+    const auto pools = loc_pools(e);
+    bool any_loc = false;
+    for (uint32_t i = 0; i < n; i++) any_loc = any_loc || (hdr[i].flags & MT_CKF_LOC);
+    {
+        uint32_t more[3];
+        for (int k = 0; k < 3; k++) {
+            const LocPool& p = pools[k];
+            uint32_t want = 0, back = (uint32_t)p.freel->size();
+            for (uint32_t i = 0; i < n; i++) {
+                want += (hdr[i].flags & p.flag) != 0;
+                back += doc_ids[i] < p.mirror->size() && (*p.mirror)[doc_ids[i]] != MT_NO_ROW;
+            }
+            more[k] = want > back ? want - back : 0;
+        }
+        if (more[0] || more[1] || more[2]) {
+            HIP_OK(hipDeviceSynchronize());  // (a grow moves the rows in use)
+            if (pool_reserve(e->nbig, e->bigcap, more[0], [&](uint32_t r) { return grow_big(e, r); }) != more[0] ||
+                pool_reserve(e->ngx, e->gxcap, more[1], [&](uint32_t r) { return grow_gx(e, r); }) != more[1] ||
+                pool_reserve(e->nwx, e->wxcap, more[2], [&](uint32_t r) { return grow_wx(e, r); }) != more[2])
+                return MT_ERR_NOMEM;
+        }
+    }
     // the slots start over as in mt_docs_load: pool rows given back, no label keys
     if (const mt_status rs = release_loc_rows(e, doc_ids, n)) return rs;
+    // every restored document gets exactly the rows its blob names (the unpack kernel reads them from the
+    // tables); the host copies per document, the device tables one copy of the changed span each
+    {
+        bool any = false;
+        for (const LocPool& p : pools) {
+            uint32_t lo = UINT32_MAX, hi = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                if (!(hdr[i].flags & p.flag)) continue;
+                const uint32_t d = doc_ids[i];
+                (*p.mirror)[d] = take_row(*p.freel, *p.used);
+                lo = std::min(lo, d);
+                hi = std::max(hi, d + 1);
+            }
+            if (lo >= hi) continue;
+            if (const mt_status st = push_loc_table(e, p, lo, hi)) return st;
+            any = true;
+        }
+        if (any) HIP_OK(hipStreamSynchronize(e->stream));
+    }
     if (e->lkeys.size() < e->cfg.max_docs) e->lkeys.resize(e->cfg.max_docs, (uint16_t)MT_NO_LABEL_KEYS);
     for (uint32_t i = 0; i < n; i++) e->lkeys[doc_ids[i]] = (uint16_t)MT_NO_LABEL_KEYS;
     e->gen++;
@@ -750,6 +816,7 @@ mt_status mt_docs_restore(mt_engine* e, const uint8_t* blob, uint64_t bytes, uin
         .launch(mt_launch_intervals_free_docs, &e->g, d_ids, n, e->n_docs, e->stream)
         .launch(hipEventRecord, e->ev0, e->stream)
         .launch(mt_launch_ckpt_unpack, &e->g, d_ids, n, d_off, d_in, ckpt_parts(max_doc), e->stream)
+        .launch(mt_launch_ckpt_unpack_loc, &e->g, d_ids, any_loc ? n : 0u, d_off, d_in, ckpt_parts(max_doc), e->stream)
         .launch(hipEventRecord, e->ev1, e->stream)
         .sync();
     if (ch.status()) return ch.status();

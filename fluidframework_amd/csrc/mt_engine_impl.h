@@ -126,6 +126,7 @@ struct mt_engine {
         void* dev = nullptr;  // one allocation: ids, headers, offsets
         size_t o_hdr = 0, o_off = 0;
         bool unsupported = false;  // a document save refuses (mt_engine.cpp ckpt_supported)
+        bool any_loc = false;      // an editing client's document among them (its sections: a launch of their own)
     } ckpt_cache;
     // mt_last_checkpoint_stats: the last pack / unpack launch by HIP events, and the blob bytes it moved
     float ckpt_pack_ms = 0.f, ckpt_unpack_ms = 0.f;

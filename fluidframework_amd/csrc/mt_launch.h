@@ -112,6 +112,12 @@ hipError_t mt_launch_ckpt_pack(const mt_gstate* g, const uint32_t* ids, uint32_t
 // the (checked) document at in + off[i] into slot ids[i]
 hipError_t mt_launch_ckpt_unpack(const mt_gstate* g, const uint32_t* ids, uint32_t n, const uint64_t* off,
                                  const uint8_t* in, uint32_t parts, hipStream_t st);
+// the editing clients' sections of the same documents (a launch of their own, after the one above, when a
+// document of the call is an editing client's; n = 0: none is, nothing is launched)
+hipError_t mt_launch_ckpt_pack_loc(const mt_gstate* g, const uint32_t* ids, uint32_t n, const struct mt_ckpt_dochdr* hdr,
+                                   const uint64_t* off, uint8_t* out, uint32_t parts, hipStream_t st);
+hipError_t mt_launch_ckpt_unpack_loc(const mt_gstate* g, const uint32_t* ids, uint32_t n, const uint64_t* off,
+                                     const uint8_t* in, uint32_t parts, hipStream_t st);
 
 // ---- mt_text.hip: text reads
 hipError_t mt_launch_text_ranges(const mt_gstate* g, const mt_text_query* q, uint32_t n, uint32_t n_docs,

@@ -621,9 +621,10 @@ class MergeEngine:
     def save_docs(self, docs=None):
         """The exact device state of documents `docs` (default: all) as one self-describing blob
         (uint8 array): restore_docs puts them into any slots of any engine that holds them, and they
-        go on bit-exactly.  Observer documents only, today: an editing client's document, or one with
-        label keys, references or intervals, raises CheckpointError.  Events not drained yet are not
-        part of it: drain them first."""
+        go on bit-exactly.  Observer documents and editing clients' documents, narrow or wide: pending
+        edits, their groups' ack order and regenerated ops not drained yet (regen_drain) travel with an
+        editing document.  A document with label keys, references or intervals raises CheckpointError.
+        Events not drained yet are not part of it: drain them first."""
         ids = np.arange(self.n_docs, dtype=np.uint32) if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
         nbytes = ctypes.c_uint64()
         blob = None
@@ -631,8 +632,8 @@ class MergeEngine:
             rc = lib().mt_docs_save(self.h, len(ids), _ptr(ids), None if blob is None else _ptr(blob),
                                     0 if blob is None else len(blob), ctypes.byref(nbytes))
             if rc == MT_ERR_CKPT:
-                raise CheckpointError('mt_docs_save: a document is not an observer document '
-                                      '(editing client, label keys, references or intervals)', 0xFFFFFFFF)
+                raise CheckpointError('mt_docs_save: a document is not admitted yet '
+                                      '(label keys, references or intervals)', 0xFFFFFFFF)
             _check(rc, 'mt_docs_save')
             if blob is None:
                 blob = np.zeros(nbytes.value, dtype=np.uint8)
@@ -640,8 +641,11 @@ class MergeEngine:
 
     def restore_docs(self, blob, docs=None, src=None):
         """Documents src[i] of the blob (default: i) into slots docs[i] (default: i); all or nothing.
-        A blob that is malformed, or a document that does not fit this engine or is not an observer
-        document, raises CheckpointError (.bad: the blob's document) and touches no slot."""
+        A blob that is malformed, or a document that does not fit this engine (an editing document:
+        at most 8192 segments) or has label keys, references or intervals, raises CheckpointError
+        (.bad: the blob's document) and touches no slot.  An editing document takes the pool rows its
+        blob names; a pool that cannot grow raises MtError (out of memory), nothing moved.  A record
+        index in a later regen_drain counts within the batch applied here, not the saving engine's."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         if src is not None:
             src = np.ascontiguousarray(src, dtype=np.uint32)

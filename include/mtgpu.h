@@ -301,11 +301,18 @@ mt_status mt_docs_load(mt_engine* eng, uint32_t n, const uint32_t* doc_ids, cons
  * one would have: same states, same checksums, same delta and maintenance callbacks.
  * The blob names no slot, stride, arena half or pool row: it restores into any slot of any engine
  * whose capacities hold the document, and saving it again there gives the same bytes.
- * TODAY both calls admit OBSERVER documents only, narrow or wide.  The format (csrc/mt_ckpt.h, version
- * 1) and the host checker also cover an editing client's pending state, declared label keys with their
- * stale block caches, local references and intervals, but a document that has any of them is refused
- * (MT_ERR_CKPT from mt_docs_save, nothing written; MT_ERR_CKPT from mt_docs_restore, no slot touched)
- * until its continuation after a restore is pinned by tests on the device.
+ * Both calls admit OBSERVER documents and EDITING CLIENTS' documents, narrow or wide, in every editing
+ * form.  An editing document's pending state travels with it: its pending groups with their stamps and
+ * localSeqs (so its acks land in the saved order), the per-segment group masks, pending property counts,
+ * creation stamps and local sequence numbers (of its 1024-slot row or its big-pool row, the group and
+ * wide pool rows it held), and the ops a reconnect regenerated that mt_regen_drain has not handed over
+ * yet.  (A regenerated op's record index counts within the batch that carried the MT_SEQ_REGEN record:
+ * after a restore the indices of later batches start over like any other engine's.)
+ * STILL REFUSED: a document with declared label keys (their stale block caches), with local references
+ * or with intervals, editing or not.  The format (csrc/mt_ckpt.h, version 1) and the host checker cover
+ * them, but such a document is refused (MT_ERR_CKPT from mt_docs_save, nothing written; MT_ERR_CKPT from
+ * mt_docs_restore, no slot touched) until its continuation after a restore is pinned by tests on the
+ * device.
  * NOT saved: the delta / maintenance events not drained yet (drain them first: mt_events_drain).
  *
  * mt_docs_save: documents doc_ids[0..n) (NULL: 0..n-1) into buf.  Two calls like mt_get_snapshots:
@@ -319,8 +326,12 @@ mt_status mt_docs_save(mt_engine* eng, uint32_t n, const uint32_t* doc_ids, uint
  * interval handles against the enabled tables) and what the call admits (above): on a failure
  * MT_ERR_CKPT, *bad = the blob document (may be NULL), and no slot is touched.  No byte of a blob that
  * fails reaches the device.
+ * Then what needs memory: the wide arrays, the staging buffer, and one row of the editing pools per
+ * restored document that held one (rows given back before come first, then the pools grow): MT_ERR_NOMEM
+ * with no slot touched.
  * The target slots start over as in mt_docs_load (pool rows given back, references and intervals
- * freed, label keys undeclared, events not drained dropped) and then hold the saved documents. */
+ * freed, label keys undeclared, events not drained dropped) and then hold the saved documents, each
+ * with exactly the kinds of pool rows it was saved with. */
 mt_status mt_docs_restore(mt_engine* eng, const uint8_t* blob, uint64_t bytes, uint32_t n, const uint32_t* src,
                           const uint32_t* doc_ids, uint32_t* bad);
 /* The last mt_docs_save's pack launch and the last mt_docs_restore's unpack launch by HIP events, and
